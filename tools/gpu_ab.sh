@@ -12,7 +12,7 @@ for round in 0 1; do
     args=""
     for kv in $set; do args="$args --option $kv"; done
     log=gpurun_out/ab_${tag}_${round}_$i.log
-    timeout -k 10 300 python bench.py --no-cpu-baseline $args > $log 2>&1 || { echo "fail: $set"; tail -5 $log; exit 1; }
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline $args > $log 2>&1 || { echo "fail: $set"; tail -5 $log; exit 1; }
     python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); k=d['kernels']; print('%-28s %9.0f' % (sys.argv[2], d['value']), {n: v['ms_per_step'] for n,v in k.items() if v.get('launches')})" $log "[$set]"
     i=$((i+1))
   done

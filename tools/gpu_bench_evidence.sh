@@ -5,7 +5,7 @@
 #   2. separate --pmc passes: FETCH_SIZE, WRITE_SIZE, the SQ counters,
 #   3. tools/prof_summary.py writes profiles/<TAG>_pmc_all.json (every kernel
 #      group) and profiles/<TAG>_pmc_<dominant>.json, stamped with the source hash,
-#   4. bench.py (default: C2 with its CPU baseline) reads them: the line carries
+#   4. bench.py --full (default: C2 with its CPU baseline) reads them: the line carries
 #      traffic / limiter / per-kernel counters of THIS build.
 # Outputs under gpurun_out/ev_<TAG>/ (profiles/<TAG>_* copied there too).
 # usage: tools/gpu_bench_evidence.sh TAG [CONFIG] [BENCH_KERNEL] [KERNEL_SUBSTR] [extra bench args...]
@@ -29,7 +29,7 @@ echo pmc_ok
 python3 tools/prof_summary.py --all "$tag" $out/prof_stats $out/prof_fetch $out/prof_write "$cfg" $out/prof_sq > $out/pmc_all.json || { echo summary_all_fail; exit 1; }
 python3 tools/prof_summary.py "$tag" $out/prof_stats $out/prof_fetch $out/prof_write "$ks" "$bk" "$cfg" $out/prof_sq > $out/pmc_one.json || { echo summary_fail; exit 1; }
 python3 tools/pmc_table.py $out/prof_fetch $out/prof_write $out/prof_sq > $out/table.txt 2>&1 || true
-timeout -k 10 600 python3 -u bench.py --config "$cfg" "$@" > $out/bench.log 2> $out/bench.err || { echo bench_fail; tail -20 $out/bench.err; exit 1; }
+timeout -k 10 600 python3 -u bench.py --full --config "$cfg" "$@" > $out/bench.log 2> $out/bench.err || { echo bench_fail; tail -20 $out/bench.err; exit 1; }
 tail -1 $out/bench.log > $out/bench_line.json
 cp profiles/${tag}_* $out/ 2>/dev/null
 cut -c1-600 $out/bench_line.json
