@@ -173,6 +173,8 @@ struct dsce_ctx {
     Opts op{};                            // kernel selection (dsce_set_option)
     JakesChunks jk{};                     // samples of the IR a batch needs (update_jakes_chunks)
     int jakes_kind = 0;                   // which Jakes kernel the last batch ran (JAKES_KIND_*)
+    JakesInfo jakes_info;                 // ... and its template instance, also of the last
+                                          // dsce_channel_realise (dsce_jakes_info)
     size_t jk_nsch = (size_t)-1;          // scheme count jk was computed for
     McBuffers buf{};
     size_t buf_key[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -1565,7 +1567,7 @@ void run_batch(dsce_ctx* c, uint64_t seed, uint64_t rep0, int R, int nvalid, Tra
         Timed t(c, "k_jakes");
         if (c->jk_nsch != c->schemes.size()) update_jakes_chunks(c);
         update_jakes_groups(c);
-        c->jakes_kind = launch_jakes(c->stream, op, c->ch, seed, rep0, R, b.ir, &c->jk);
+        c->jakes_kind = launch_jakes(c->stream, op, c->ch, seed, rep0, R, b.ir, &c->jk, &c->jakes_info);
     }
     const int chunk = snr_chunk(c);
     for (size_t si = 0; si < c->schemes.size(); ++si) {
@@ -2158,7 +2160,7 @@ static int add_scheme_one(dsce_ctx* ctx, const dsce_scheme_desc* d, int32_t* sch
         d->n_tx_symbols != d->n_pilots + d->n_data)
         throw ApiError(DSCE_EINVAL, "inconsistent scheme dimensions");
     if (d->mod_order < 2 || d->mod_order > 256 || (d->mod_order & (d->mod_order - 1)) ||
-        (1 << d->bits_per_symbol) != d->mod_order || 32 % d->bits_per_symbol)
+        (1 << d->bits_per_symbol) != d->mod_order)
         throw ApiError(DSCE_EINVAL, "modulation order must be a power of two <= 256");
     if (!d->despread && !d->data_pos) throw ApiError(DSCE_EINVAL, "data_pos required in select mode");
     if (d->kappa <= 0 || d->data_div <= 0) throw ApiError(DSCE_EINVAL, "kappa/data_div must be positive");
@@ -2429,9 +2431,9 @@ int dsce_channel_realise(dsce_ctx* ctx, uint64_t seed, uint64_t rep, double* ir_
         if (ctx->jk_nsch != ctx->schemes.size()) update_jakes_chunks(ctx);
         update_jakes_groups(ctx);
         DSCE_HIP_CHECK(hipMemsetAsync(ir, 0, (size_t)ctx->ch.ntap * N * R * sizeof(double2), ctx->stream));
-        launch_jakes(ctx->stream, ctx->op, ctx->ch, seed, rep - (uint64_t)lane, R, ir, &ctx->jk);
+        launch_jakes(ctx->stream, ctx->op, ctx->ch, seed, rep - (uint64_t)lane, R, ir, &ctx->jk, &ctx->jakes_info);
     } else {
-        launch_jakes(ctx->stream, ctx->op, ctx->ch, seed, rep - (uint64_t)lane, R, ir);
+        launch_jakes(ctx->stream, ctx->op, ctx->ch, seed, rep - (uint64_t)lane, R, ir, nullptr, &ctx->jakes_info);
     }
     std::vector<double2> h((size_t)ctx->ch.ntap * N * R);
     DSCE_HIP_CHECK(hipMemcpyAsync(h.data(), ir, h.size() * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
@@ -2953,6 +2955,20 @@ int dsce_path_info(dsce_ctx* ctx, int32_t id, uint32_t* flags) {
     Scheme& s = get_scheme(ctx, id);
     if (!flags) throw ApiError(DSCE_EINVAL, "null output");
     *flags = s.path;
+    API_END
+}
+
+int dsce_jakes_info(dsce_ctx* ctx, int32_t* out6) {
+    API_BEGIN
+    check_ctx(ctx);
+    if (!out6) throw ApiError(DSCE_EINVAL, "null output");
+    const JakesInfo& ji = ctx->jakes_info;
+    out6[0] = ji.kernel;
+    out6[1] = ji.grp2;
+    out6[2] = ji.ngrp;
+    out6[3] = ji.lg;
+    out6[4] = ji.mt;
+    out6[5] = ji.nchunk;
     API_END
 }
 

@@ -180,8 +180,17 @@ constexpr double JAKES_XMAX = 3.0;
 // which kernel ran (the work model of dsce_kernel_work): JAKES_KIND_GRP
 // k_jakes_grp, JAKES_KIND_MOM k_jakes_mom, else JAKES_KIND_OTHER.
 enum { JAKES_KIND_OTHER = 0, JAKES_KIND_MOM = 2, JAKES_KIND_GRP = 3 };
+// Which kernel and template instance launch_jakes chose (dsce_jakes_info; the
+// kernel values are mirrored in include/dsce.h DSCE_JAKES_*): ngrp / lg / mt
+// of the grouped kernels' instance (0 elsewhere), nchunk the window chunks
+// formed (0: every sample).
+struct JakesInfo {
+    int kernel = 0, grp2 = 0, ngrp = 0, lg = 0, mt = 0, nchunk = 0;
+};
+enum { JAKES_K_NONE = 0, JAKES_K_STATIC = 1, JAKES_K_DISCRETE = 2, JAKES_K_FULL = 3, JAKES_K_WIN_REC = 4,
+       JAKES_K_WIN_MOM = 5, JAKES_K_WIN_GRP = 6 };
 int launch_jakes(hipStream_t s, const Opts& op, const ChannelK& ch, uint64_t seed, uint64_t rep0, int R,
-                  double2* ir, const JakesChunks* jc = nullptr);
+                  double2* ir, const JakesChunks* jc = nullptr, JakesInfo* info = nullptr);
 // txrx (txrx_fft_ok): only the symbols; k_txrx_fft forms s, r0 and diag(D) in
 // launch_rx_front
 void launch_tx(hipStream_t s, const SchemeK& sk, const ChannelK& ch, int bits_slot, int pilot_slot, uint64_t seed,

@@ -890,12 +890,17 @@ __global__ void __launch_bounds__(64) k_discrete(ChannelK ch, uint64_t seed, uin
 }
 
 int launch_jakes(hipStream_t s, const Opts& op, const ChannelK& ch, uint64_t seed, uint64_t rep0, int R,
-                  double2* ir, const JakesChunks* jc) {
+                  double2* ir, const JakesChunks* jc, JakesInfo* info) {
+    JakesInfo scratch;
+    JakesInfo& ji = info ? *info : scratch;
+    ji = JakesInfo{};
     if (ch.fD == 0.0) {
+        ji.kernel = JAKES_K_STATIC;
         hipLaunchKernelGGL(k_static, dim3(R / WAVE, (ch.N + 63) / 64, ch.ntap), dim3(WAVE), 0, s, ch, seed, rep0, R, ir);
         return JAKES_KIND_OTHER;
     }
     if (ch.model >= 2) {
+        ji.kernel = JAKES_K_DISCRETE;
         hipLaunchKernelGGL(k_discrete, dim3(R / WAVE, (ch.N + DCH - 1) / DCH, ch.ntap), dim3(WAVE), 0, s, ch, seed,
                            rep0, R, ir);
         return JAKES_KIND_OTHER;
@@ -905,6 +910,7 @@ int launch_jakes(hipStream_t s, const Opts& op, const ChannelK& ch, uint64_t see
     // splitting the paths (12-sample chunks, one lane each: 2.37 ms per
     // 65536 realisations at C2, the per-chunk cis ~45 % of the instructions)
     if (jc && jc->n0 && op.jakes_win && R % 8 == 0 && (size_t)8 * 4 * ch.paths * sizeof(double) <= 64 * 1024) {
+        ji.nchunk = jc->n;
         // the phase-moment form where its Taylor remainder is negligible
         // (|theta| (LEN - 1) / 2 <= 0.3), else the recurrence
         // two non-zero taps and 1 / 2 / 4 anchor groups: both taps in one wave
@@ -915,6 +921,7 @@ int launch_jakes(hipStream_t s, const Opts& op, const ChannelK& ch, uint64_t see
             const size_t lds = (size_t)32 * ch.paths * sizeof(double);
 #define LAUNCH_JGRP2(MT_, NG_)                                                                                 \
     if (jc->mt == MT_ && jc->ngrp == NG_) {                                                                   \
+        ji = JakesInfo{JAKES_K_WIN_GRP, 1, NG_, 16 / NG_, MT_, jc->n};                                        \
         hipLaunchKernelGGL((k_jakes_grp2<MT_, 16 / NG_>), grid, dim3(256), lds, s, ch, seed, rep0, R, ir,     \
                            jc->n0, jc->grp, jc->ngrp);                                                        \
         return JAKES_KIND_GRP;                                                                                \
@@ -931,6 +938,7 @@ int launch_jakes(hipStream_t s, const Opts& op, const ChannelK& ch, uint64_t see
             const size_t lds = (size_t)4 * RPW * 3 * ch.paths * sizeof(double);
 #define LAUNCH_JGRP(MT_, LG_)                                                                                 \
     if (jc->mt == MT_ && jc->lg == LG_) {                                                                    \
+        ji = JakesInfo{JAKES_K_WIN_GRP, 0, jc->ngrp, LG_, MT_, jc->n};                                       \
         hipLaunchKernelGGL((k_jakes_grp<MT_, LG_>), grid, dim3(256), lds, s, ch, seed, rep0, R, ir, jc->n0,  \
                            jc->grp, jc->ngrp);                                                               \
         return JAKES_KIND_GRP;                                                                               \
@@ -943,16 +951,19 @@ int launch_jakes(hipStream_t s, const Opts& op, const ChannelK& ch, uint64_t see
         if (op.jakes_mom && JakesChunks::LEN == 24 && TWO_PI * fabs(ch.fD) * ch.dt * 11.5 <= 0.3) {
             constexpr int RPW = 2, CPW = WAVE / RPW / 2;
             dim3 grid((jc->n + CPW - 1) / CPW, R / (4 * RPW), ch.ntap);
+            ji.kernel = JAKES_K_WIN_MOM;
             hipLaunchKernelGGL((k_jakes_mom<RPW, 12>), grid, dim3(256), (size_t)4 * RPW * 3 * ch.paths * sizeof(double),
                                s, ch, seed, rep0, R, ir, jc->n0, jc->n);
             return JAKES_KIND_MOM;
         }
+        ji.kernel = JAKES_K_WIN_REC;
         launch_jakes_t<JakesChunks::LEN, 2, 2>(s, ch, seed, rep0, R, ir, jc->n0, jc->n);
         return JAKES_KIND_OTHER;
     }
     // two realisations per wave (32 lanes each) when that gives chunks of 9-20
     // samples (N 257-640) and R splits into blocks of 8; the LDS path tables
     // then take 64 P bytes per realisation, 51 KB per block at P = 200
+    ji.kernel = JAKES_K_FULL;
     const int jch2 = (ch.N + WAVE / 2 - 1) / (WAVE / 2);
     if (jch2 >= 9 && jch2 <= 20 && R % 8 == 0 && (size_t)8 * 4 * ch.paths * sizeof(double) <= 64 * 1024 &&
         op.jakes_rpw == 2) {
@@ -1333,6 +1344,28 @@ struct StorePerfectDetect {
     }
 };
 
+// Data symbol index (bi2de, LSB first) of the mbits bits starting at bit q of
+// the BITS stream (include/dsce.h: bit i is bit (i & 31) of word (i >> 5) & 3 of
+// counter i >> 7).  When mbits divides 32 a symbol never leaves its word; 3- and
+// 6-bit symbols (8-PAM, 64-QAM) can straddle into the next word, which may be
+// the first of the next counter.  q is the same in every lane (lane =
+// realisation), so the branch is wave-uniform.
+__device__ __forceinline__ uint32_t stream_word(uint4 w, uint32_t wi) {
+    return wi == 0 ? w.x : wi == 1 ? w.y : wi == 2 ? w.z : w.w;
+}
+__device__ __forceinline__ uint16_t data_index(uint64_t seed, uint64_t rep, int bits_slot, uint32_t q, int mbits,
+                                               uint32_t mmask) {
+    const uint4 w = stream_block(seed, rep, STREAM_BITS, bits_slot, q >> 7);
+    uint32_t v = stream_word(w, (q >> 5) & 3) >> (q & 31);
+    const uint32_t have = 32u - (q & 31);
+    if (have < (uint32_t)mbits) {
+        const uint32_t q2 = q + have;                           // first bit of the next word
+        const uint4 w2 = (q2 >> 7) == (q >> 7) ? w : stream_block(seed, rep, STREAM_BITS, bits_slot, q2 >> 7);
+        v |= stream_word(w2, (q2 >> 5) & 3) << have;
+    }
+    return (uint16_t)(v & mmask);
+}
+
 // ---------------------------------------------------------------------------
 // a7: TX chain, lane = realisation.  Pilots (script:365-368), data symbols from
 // bits (script:355-362), x = P [xP; xD] (script:371-373).
@@ -1356,10 +1389,7 @@ __global__ void __launch_bounds__(64) k_tx_symbols(SchemeK sk, int bits_slot, in
     }
     for (int i = 0; i < sk.ND; ++i) {
         const uint32_t q = (uint32_t)(i * sk.mbits);               // first bit of symbol i
-        const uint4 w = stream_block(seed, rep, STREAM_BITS, bits_slot, q >> 7);
-        const uint32_t wi = (q >> 5) & 3;
-        const uint32_t word = wi == 0 ? w.x : wi == 1 ? w.y : wi == 2 ? w.z : w.w;
-        const uint16_t si = (uint16_t)((word >> (q & 31)) & mmask);   // bi2de, LSB first
+        const uint16_t si = data_index(seed, rep, bits_slot, q, sk.mbits, mmask);   // bi2de, LSB first
         sidx[(size_t)i * R + rl] = si;
         // the same, row-indexed (select mode only: data_pos holds one dummy entry
         // for a data-spreading scheme, whose data symbols have no rows)
@@ -1407,10 +1437,7 @@ __global__ void __launch_bounds__(64) k_tx_rows(SchemeK sk, int bits_slot, int p
         } else if (k >= sk.NP) {
             const int i = k - sk.NP;
             const uint32_t q = (uint32_t)(i * sk.mbits);
-            const uint4 w = stream_block(seed, rep, STREAM_BITS, bits_slot, q >> 7);
-            const uint32_t wi = (q >> 5) & 3;
-            const uint32_t word = wi == 0 ? w.x : wi == 1 ? w.y : wi == 2 ? w.z : w.w;
-            const uint16_t si = (uint16_t)((word >> (q & 31)) & mmask);
+            const uint16_t si = data_index(seed, rep, bits_slot, q, sk.mbits, mmask);
             sidx[(size_t)i * R + rl] = si;
             sidr[(size_t)r * R + rl] = si;
             c_fma(acc, sk.row_pval[r], sym[si]);

@@ -24,10 +24,13 @@ EXPORTED = [
     "dsce_set_noise_slot", "dsce_set_interpolation", "dsce_enable_mse", "dsce_get_mse", "dsce_trace_unit_ex",
     "dsce_scheme_dims", "dsce_path_info", "dsce_set_option", "dsce_get_option", "dsce_fp64_mfma_peak",
     "dsce_kernel_work", "dsce_structured_check", "dsce_create_multi", "dsce_group_info",
-    "dsce_transmission_matrix",
+    "dsce_transmission_matrix", "dsce_jakes_info",
 ]
 
-ABI_VERSION = 7
+ABI_VERSION = 8
+
+# dsce_jakes_info kernels (include/dsce.h DSCE_JAKES_*)
+JAKES_KERNELS = {0: "none", 1: "static", 2: "discrete", 3: "full", 4: "win_rec", 5: "win_mom", 6: "win_grp"}
 
 # dsce_group_info reduce kinds (include/dsce.h DSCE_REDUCE_*)
 REDUCE = {0: "none", 1: "rccl", 2: "host"}
@@ -128,6 +131,7 @@ def load_library(path=None):
     lib.dsce_trace_unit_ex.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.POINTER(Trace)]
     lib.dsce_scheme_dims.argtypes = [vp, C.c_int32, C.POINTER(Dims)]
     lib.dsce_path_info.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint32)]
+    lib.dsce_jakes_info.argtypes = [vp, C.POINTER(C.c_int32)]
     lib.dsce_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
     lib.dsce_get_option.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int64)]
     lib.dsce_fp64_mfma_peak.argtypes = [vp, dp]
@@ -366,6 +370,17 @@ class Engine:
         f = C.c_uint32()
         self._chk(self.lib.dsce_path_info(self.h, int(sid), C.byref(f)), "dsce_path_info")
         return {k for k, bit in PATH_BITS.items() if f.value & bit}
+
+    def jakes_info(self):
+        """The Jakes kernel of the last run / trace / channel_impulse_response
+        (dsce_jakes_info): dict with kernel ('static' | 'discrete' | 'full' |
+        'win_rec' | 'win_mom' | 'win_grp'; 'none' before the first), and for
+        'win_grp' grp2 (k_jakes_grp2 instead of k_jakes_grp), ngrp, lg, mt (the
+        template instance <mt, lg>); chunks = window chunks formed (0: all samples)."""
+        out = (C.c_int32 * 6)()
+        self._chk(self.lib.dsce_jakes_info(self.h, out), "dsce_jakes_info")
+        return dict(kernel=JAKES_KERNELS.get(out[0], str(out[0])), grp2=bool(out[1]), ngrp=out[2], lg=out[3],
+                    mt=out[4], chunks=out[5])
 
     def set_option(self, name, value):
         self._chk(self.lib.dsce_set_option(self.h, name.encode(), int(value)), "dsce_set_option(%s)" % name)

@@ -79,7 +79,7 @@
 extern "C" {
 #endif
 
-#define DSCE_ABI_VERSION 7
+#define DSCE_ABI_VERSION 8
 
 #define DSCE_OK 0
 #define DSCE_EINVAL -1      /* bad argument / shape */
@@ -117,8 +117,9 @@ typedef struct {
     int32_t n_tx_symbols;       /* columns of P: NP + ND                       */
     int32_t n_pilots;           /* NP                                          */
     int32_t n_data;             /* ND                                          */
-    int32_t mod_order;          /* M (power of two)                            */
-    int32_t bits_per_symbol;    /* log2(M)                                     */
+    int32_t mod_order;          /* M (power of two, 2..256; larger: DSCE_EINVAL) */
+    int32_t bits_per_symbol;    /* log2(M); any of 1..8 (3- and 6-bit symbols   */
+                                /* straddle the BITS stream's words, ABI 8)     */
     int32_t despread;           /* 1: x_hat = P^H (y./h), data = entries NP..  (script:436) */
     int32_t real_detect;        /* 1: real() before detection (FBMC-OQAM)      */
     int32_t bits_slot;          /* RNG sub-stream for the data bits            */
@@ -215,6 +216,17 @@ typedef struct {
                                                  (k_poly_syn / k_poly_chan / k_poly_ana, option pic_poly) */
 #define DSCE_PATH_WROW3           (1u << 17)  /* unfused W contraction of 32-row blocks as one GEMM per row tile,
                                                  B = hP v_c (k_wrow3, option wrow) */
+
+/* Jakes kernels (dsce_jakes_info out6[0]) */
+#define DSCE_JAKES_NONE      0   /* no realisation formed yet                                        */
+#define DSCE_JAKES_STATIC    1   /* k_static: max_doppler == 0, one value per realisation and tap      */
+#define DSCE_JAKES_DISCRETE  2   /* k_discrete: the discrete Doppler models                            */
+#define DSCE_JAKES_FULL      3   /* k_jakes, recurrence over every sample (no read windows, option     */
+                                 /* jakes_win 0, or more than 256 paths: the windows' LDS tables do    */
+                                 /* not fit)                                                           */
+#define DSCE_JAKES_WIN_REC   4   /* k_jakes<24, 2, 2>: the recurrence over the read windows            */
+#define DSCE_JAKES_WIN_MOM   5   /* k_jakes_mom: one Taylor anchor per window                          */
+#define DSCE_JAKES_WIN_GRP   6   /* k_jakes_grp / k_jakes_grp2: Taylor anchors over runs of windows    */
 
 int dsce_abi_version(void);
 int dsce_device_count(int* count);
@@ -346,6 +358,15 @@ int dsce_trace_unit_ex(dsce_ctx* ctx, int32_t scheme_id, uint64_t seed, uint64_t
 int dsce_scheme_dims(dsce_ctx* ctx, int32_t scheme_id, dsce_dims* dims);
 /* Which kernels a scheme's last dsce_run / trace used: DSCE_PATH_* bits. */
 int dsce_path_info(dsce_ctx* ctx, int32_t scheme_id, uint32_t* flags);
+/* Which Jakes kernel and template instance formed the channel taps of the last
+ * dsce_run batch / trace or dsce_channel_realise (ABI 8; read-only):
+ * out6[0] = DSCE_JAKES_*; and for DSCE_JAKES_WIN_GRP out6[1] = 1 for
+ * k_jakes_grp2<mt, lg> (both taps of a two-tap channel per wave, lg = 16 /
+ * groups), 0 for k_jakes_grp<mt, lg>, out6[2] = anchor groups, out6[3] = lg
+ * lanes per anchor (4 | 8 | 16), out6[4] = mt Taylor terms (16 | 24 | 28)
+ * (all 0 for the other kernels); out6[5] = the 24-sample window chunks formed
+ * (0: every sample). */
+int dsce_jakes_info(dsce_ctx* ctx, int32_t* out6);
 /* Kernel-selection options (defaults = the measured-best path; each other value
  * selects a real fallback, reached by the parity tests):
  *   xcd (XCD-aware work order), fuse_stage (MMSE stage in the contraction's

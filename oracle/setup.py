@@ -461,13 +461,23 @@ _CONFIGS = {
 }
 
 
-def script_setup(name="default", schemes=("fbmc_aux", "fbmc_cod", "ofdm"), snr_db=None, n_iter=4):
+def script_setup(name="default", schemes=("fbmc_aux", "fbmc_cod", "ofdm"), snr_db=None, n_iter=4, *,
+                 qam_order=256, pdp="VehicularA", velocity_kmh=500.0, paths=200, doppler_model="Jakes"):
     """Everything the script builds before its Monte-Carlo loop, as the plain
-    dicts oracle/refsim.simulate and mmse_setup consume."""
+    dicts oracle/refsim.simulate and mmse_setup consume.  The keyword
+    parameters are the script's own (QAM_ModulationOrder script:29, and the
+    FastFading arguments PowerDelayProfile, Velocity_kmh, the number of paths
+    and the Doppler model, script:176-186); the PAM order follows as
+    sqrt(qam_order) (script:86-87).  The defaults are the script's."""
     L, srm, nsub, snr = _CONFIGS[name]
     F = 15e3
     SR = F * srm
-    qam_order, p2d, p2d_aux = 256, 2.0, 4.685
+    s_axis = int(round(np.sqrt(qam_order)))
+    if s_axis * s_axis != qam_order or s_axis < 2 or s_axis & (s_axis - 1):
+        raise ValueError("qam_order must be a square power of two (4, 16, 64, ...)")
+    if doppler_model not in ("Jakes", "Uniform"):
+        raise ValueError("doppler_model must be 'Jakes' or 'Uniform' (the sum-of-sinusoids models)")
+    p2d, p2d_aux = 2.0, 4.685
     snr = np.asarray(snr if snr_db is None else snr_db, dtype=float)
     fb = FBMC(L, 30 * nsub, F, SR, 0, 8, 0)                             # script:51-62
     zg = ((fb.N - (mround((1 / 15e3 / 14) * SR) + mround(SR / 15e3)) * 14 * nsub) / 2) / SR     # :66
@@ -544,9 +554,11 @@ def script_setup(name="default", schemes=("fbmc_aux", "fbmc_cod", "ofdm"), snr_d
                            real_detect=False, data_div=float(np.sqrt(dpr)), kappa=float(p2d * dpr), symbols=qam[0],
                            bitmap=qam[1].astype(np.uint8), bits_per_symbol=qam[1].shape[1], n_data=ND_ofdm,
                            considered=cm, bits_slot=2, pilot_slot=1)
-    pdp, pdpn, taps = power_delay_profile(SR, "VehicularA")              # script:176-186
-    fD = 500 / 3.6 * 2.5e9 / 2.998e8
-    chan = dict(N=N, dt=1.0 / SR, pdp=pdp, pdp_norm=pdpn, idx_taps=taps, fD=fD, paths=200, model="Jakes")
+    pdpv, pdpn, taps = power_delay_profile(SR, pdp)                      # script:176-186
+    fD = velocity_kmh / 3.6 * 2.5e9 / 2.998e8
+    chan = dict(N=N, dt=1.0 / SR, pdp=pdpv, pdp_norm=pdpn, idx_taps=taps, fD=fD, paths=int(paths),
+                model=doppler_model)
     pn = SR / (F * L) * 10.0 ** (-snr / 10)                             # script:243 / :398
     return dict(name=name, N=N, L=L, SR=SR, snr_db=snr, pn_time=pn, n_iter=n_iter, zero_threshold=1e-8,
-                chan=chan, schemes=out, fbmc=fb, ofdm=of)
+                chan=chan, schemes=out, fbmc=fb, ofdm=of,
+                variant=(int(qam_order), str(pdp), float(velocity_kmh), int(paths), str(doppler_model)))

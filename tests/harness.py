@@ -27,16 +27,22 @@ for p in (ROOT, PKG):
 
 
 @functools.lru_cache(maxsize=8)
-def _script_setup(name, schemes, snr_db, n_iter):
+def _script_setup(name, schemes, snr_db, n_iter, qam_order, pdp, velocity_kmh, paths, doppler_model):
     from oracle import setup as osu
-    return osu.script_setup(name, schemes=schemes, snr_db=None if snr_db is None else list(snr_db), n_iter=n_iter)
+    return osu.script_setup(name, schemes=schemes, snr_db=None if snr_db is None else list(snr_db), n_iter=n_iter,
+                            qam_order=qam_order, pdp=pdp, velocity_kmh=velocity_kmh, paths=paths,
+                            doppler_model=doppler_model)
 
 
-def setup(name="default", schemes=("fbmc_aux", "fbmc_cod", "ofdm"), snr_db=None, n_iter=4):
+def setup(name="default", schemes=("fbmc_aux", "fbmc_cod", "ofdm"), snr_db=None, n_iter=4, qam_order=256,
+          pdp="VehicularA", velocity_kmh=500.0, paths=200, doppler_model="Jakes"):
     """The oracle's restatement of the script's setup (script:16-205) as a
     namespace: N, L, pn_time, snr_db, n_iter, zero_threshold, chan (dict),
-    schemes (name -> oracle scheme dict), fbmc / ofdm (modulator objects)."""
-    d = _script_setup(name, tuple(schemes), None if snr_db is None else tuple(float(x) for x in snr_db), n_iter)
+    schemes (name -> oracle scheme dict), fbmc / ofdm (modulator objects),
+    variant (the script parameters qam_order, pdp, velocity_kmh, paths,
+    doppler_model it was built for; the defaults are the script's)."""
+    d = _script_setup(name, tuple(schemes), None if snr_db is None else tuple(float(x) for x in snr_db), n_iter,
+                      int(qam_order), str(pdp), float(velocity_kmh), int(paths), str(doppler_model))
     return SimpleNamespace(**d)
 
 
@@ -50,7 +56,7 @@ _MMSE = {}
 def oracle_mmse(S, name):
     """R_hP, R_est, R_noI, R_Dij, W, W0 of scheme `name` (refsim.mmse_setup,
     script:208-313) from the oracle's own G / Q / P and channel (cached)."""
-    key = (S.name, tuple(S.snr_db), S.n_iter, tuple(sorted(S.schemes)), name, S.zero_threshold)
+    key = (S.name, tuple(S.snr_db), S.n_iter, tuple(sorted(S.schemes)), name, S.zero_threshold, tuple(S.variant))
     if key not in _MMSE:
         from oracle import refsim
         ch = S.chan
@@ -79,9 +85,12 @@ def _engine_scheme(S, name):
                            extras={"pilot_matrix": np.zeros((S.L, sc["G"].shape[1] // S.L))})
 
 
-def engine(S, schemes=None, batch=None, options=None, device=0):
+def engine(S, schemes=None, batch=None, options=None, device=0, mmse=True):
     """dsce.engine.Engine built from the oracle setup S (channel, SNR list,
-    schemes, MMSE build), like dsce.engine.build_engine does from dsce.configs."""
+    schemes, MMSE build), like dsce.engine.build_engine does from dsce.configs.
+    mmse=False leaves dsce_build_mmse out: enough for the channel probes
+    (channel_impulse_response), which read only the channel and the schemes'
+    Q^H windows."""
     from dsce.engine import Engine
     ch = S.chan
     eng = Engine(device)
@@ -94,7 +103,8 @@ def engine(S, schemes=None, batch=None, options=None, device=0):
     eng.set_snr(S.pn_time, S.n_iter)
     for n in (list(S.schemes) if schemes is None else list(schemes)):
         eng.add_scheme(_engine_scheme(S, n))
-    eng.build_mmse(S.zero_threshold)
+    if mmse:
+        eng.build_mmse(S.zero_threshold)
     if batch:
         eng.set_batch(batch)
     return eng

@@ -73,6 +73,24 @@ def test_no_cpu_fallback_without_gpu():
         engine.Engine([0, 1])                    # dsce_create_multi (ABI 7) fails loudly too
 
 
+def test_jakes_info_is_exported_and_rejects_null():
+    """dsce_jakes_info (ABI 8): exported, bound, and a null context is a clean
+    DSCE_EINVAL (no HIP call is made for it, so this needs no GPU)."""
+    if not os.path.exists(LIB):
+        pytest.skip("libdsce.so not built")
+    import ctypes
+
+    from dsce import engine
+    assert "dsce_jakes_info" in engine.EXPORTED and engine.ABI_VERSION >= 8
+    lib = engine.load_library()
+    out = (ctypes.c_int32 * 6)()
+    assert lib.dsce_jakes_info(None, out) == -1          # DSCE_EINVAL
+    assert sorted(engine.JAKES_KERNELS) == list(range(7))
+    txt = open(HDR).read()
+    for v, name in engine.JAKES_KERNELS.items():
+        assert re.search(r"#define DSCE_JAKES_%s\s+%d\b" % (name.upper(), v), txt), name
+
+
 def test_library_links_rccl_and_roctx():
     """The in-library all-reduce (dsce_create_multi) and the host trace ranges
     (roctx) are linked dependencies of libdsce.so."""
