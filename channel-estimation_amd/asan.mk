@@ -24,7 +24,8 @@ $(ASAN_DIR)/asan_driver.o: $(ROOT)/../tools/asan/asan_driver.cpp $(ROOT)/../incl
 	@mkdir -p $(ASAN_DIR)
 	$(HIPCC) $(FLAGS) $(ASAN_FLAGS) $(INC) -c $< -o $@
 
-$(ASAN_BIN): $(ASAN_DIR)/asan_driver.o $(ASAN_DIR)/dsce_api.o $(ROOT)/build/kernels_mc.o $(ROOT)/build/kernels_setup.o
+$(ASAN_BIN): $(ASAN_DIR)/asan_driver.o $(ASAN_DIR)/dsce_api.o $(ROOT)/build/kernels_mc.o $(ROOT)/build/kernels_setup.o \
+             $(ROOT)/build/kernels_export.o
 	$(HIPCC) $(FLAGS) $(ASAN_FLAGS) $^ -o $@ $(LIBS)
 
 clean:

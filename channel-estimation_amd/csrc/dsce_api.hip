@@ -179,6 +179,10 @@ struct dsce_ctx {
     McBuffers buf{};
     size_t buf_key[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::vector<void*> buf_allocs;
+    // device staging of one batch of dsce_export's host destinations (allocated
+    // on the first host export, grown when a later one needs more)
+    void* exp_stage = nullptr;
+    size_t exp_stage_bytes = 0;
     unsigned long long* d_counters = nullptr;
     size_t counters_n = 0;
     // pinned host copy of the counters (r06: the per-run copy back is a direct
@@ -2047,6 +2051,7 @@ int dsce_destroy(dsce_ctx* ctx) {
     note(hipSetDevice(ctx->device), "hipSetDevice");
     if (ctx->stream) note(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
     for (void* p : ctx->buf_allocs) note(hipFree(p), "hipFree (batch buffers)");
+    if (ctx->exp_stage) note(hipFree(ctx->exp_stage), "hipFree (export staging)");
     for (void* p : ctx->allocs) note(hipFree(p), "hipFree (operators)");
     if (ctx->h_counters) note(hipHostFree(ctx->h_counters), "hipHostFree (counters)");
     for (auto& e : ctx->pending) {
@@ -2403,6 +2408,137 @@ int dsce_run(dsce_ctx* ctx, uint64_t seed, uint64_t first_rep, uint64_t n_rep, i
         run_reps(ctx, seed, first_rep, n_rep);
         finish_run(ctx, err_counts, &ctx->mse_host);
     }
+    API_END
+}
+
+// Bulk export (ABI 9): the front of run_batch (Jakes, TX, receiver front) for one
+// scheme, then k_export per SNR chunk.  No IC stage, no counters, no MSE sums,
+// Scheme::path untouched.  On a multi-device handle the handle itself is member 0.
+int dsce_export(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, uint64_t n_rep, uint32_t flags,
+                const dsce_export_out* out) {
+    TraceRange trace_range("dsce export");
+    API_BEGIN
+    check_ctx(ctx);
+    if (!ctx->chan_set) throw ApiError(DSCE_ESTATE, "dsce_set_channel first");
+    if (ctx->nsnr <= 0) throw ApiError(DSCE_ESTATE, "dsce_set_snr first");
+    if (ctx->schemes.empty()) throw ApiError(DSCE_ESTATE, "no scheme added");
+    Scheme& s = get_scheme(ctx, id);
+    if (!out) throw ApiError(DSCE_EINVAL, "dsce_export: null out");
+    if (flags & ~(uint32_t)(DSCE_EXPORT_F32 | DSCE_EXPORT_DEVICE)) throw ApiError(DSCE_EINVAL, "dsce_export: unknown flag");
+    // fields in k_export's order
+    void* dst[6] = {out->y, out->hp_ls, out->h_est, out->h, out->xp, out->sym};
+    bool any = false;
+    for (void* p : dst) any = any || p;
+    if (!any) throw ApiError(DSCE_EINVAL, "dsce_export: no field requested");
+    if (out->h_est && !(s.mmse_ready && s.Wd))
+        throw ApiError(DSCE_ESTATE, "dsce_export: h_est needs dsce_build_mmse or dsce_set_interpolation");
+    const bool f32 = (flags & DSCE_EXPORT_F32) != 0, to_device = (flags & DSCE_EXPORT_DEVICE) != 0;
+    if (to_device)
+        for (void* p : dst) {
+            if (!p) continue;
+            hipPointerAttribute_t at{};
+            const hipError_t e = hipPointerGetAttributes(&at, p);
+            if (e != hipSuccess) (void)hipGetLastError();
+            if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != ctx->device)
+                throw ApiError(DSCE_EINVAL, "dsce_export: DSCE_EXPORT_DEVICE with a pointer that is not device memory "
+                                            "of the context's GPU");
+        }
+    const int LK = s.LK, NP = s.d.n_pilots, ND = s.d.n_data, nsnr = ctx->nsnr;
+    const size_t csz = f32 ? sizeof(float2) : sizeof(double2);
+    // elements per realisation and element size of each field
+    const size_t per_rep[6] = {(size_t)nsnr * LK, (size_t)nsnr * NP, (size_t)nsnr * LK, (size_t)LK, (size_t)NP, (size_t)ND};
+    const size_t esz[6] = {csz, csz, csz, csz, csz, sizeof(int32_t)};
+    const int flen[6] = {LK, NP, LK, LK, NP, ND};
+    const int chunk = snr_chunk(ctx);
+    uint64_t done = 0;
+    while (done < n_rep) {
+        const uint64_t left = n_rep - done;
+        const int R = (int)std::min<uint64_t>((uint64_t)ctx->batch, (left + 63) / 64 * 64);
+        const int nvalid = (int)std::min<uint64_t>((uint64_t)R, left);
+        const uint64_t rep0 = first_rep + done;
+        ensure_buffers(ctx, ctx->batch);
+        McBuffers& b = ctx->buf;
+        b.R = R;
+        b.rvalid = nvalid;
+        b.tr = nullptr;
+        b.mse_err = b.mse_pow = nullptr;
+        ExportK ek{};
+        ek.row0 = to_device ? (long long)done : 0;
+        if (to_device) {
+            for (int f = 0; f < 6; ++f) ek.out[f] = dst[f];
+        } else {
+            // one batch of every requested field, each 256-byte aligned
+            size_t off[6], total = 0;
+            for (int f = 0; f < 6; ++f) {
+                off[f] = total;
+                if (dst[f]) total += ((size_t)nvalid * per_rep[f] * esz[f] + 255) / 256 * 256;
+            }
+            if (total > ctx->exp_stage_bytes) {
+                if (ctx->exp_stage) {
+                    DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+                    DSCE_HIP_CHECK(hipFree(ctx->exp_stage));
+                }
+                ctx->exp_stage = nullptr;
+                ctx->exp_stage_bytes = 0;
+                DSCE_HIP_CHECK(hipMalloc(&ctx->exp_stage, total));
+                ctx->exp_stage_bytes = total;
+            }
+            for (int f = 0; f < 6; ++f) ek.out[f] = dst[f] ? (char*)ctx->exp_stage + off[f] : nullptr;
+        }
+        {
+            Timed t(ctx, "k_jakes");
+            if (ctx->jk_nsch != ctx->schemes.size()) update_jakes_chunks(ctx);
+            update_jakes_groups(ctx);
+            ctx->jakes_kind = launch_jakes(ctx->stream, ctx->op, ctx->ch, seed, rep0, R, b.ir, &ctx->jk, &ctx->jakes_info);
+        }
+        {
+            Timed t(ctx, "tx");
+            b.U = R * std::min(chunk, nsnr);
+            launch_tx(ctx->stream, s.k, ctx->ch, s.d.bits_slot, s.d.pilot_slot, seed, rep0, b,
+                      txrx_fft_ok(ctx->op, s.k, ctx->ch, b), ctx->op.tx_rows != 0);
+        }
+        ek.y = b.y;
+        ek.h = b.h;
+        ek.xp = b.xp;
+        ek.sidx = b.sidx;
+        ek.wd = s.Wd;                       // variant 0: [snr][LK][NP]
+        ek.hp = b.hp;
+        ek.pilot_pos = s.k.pilot_pos;
+        ek.inv_sqrt_kappa = s.k.inv_sqrt_kappa;
+        ek.LK = LK;
+        ek.NP = NP;
+        ek.ND = ND;
+        ek.R = R;
+        ek.nsnr = nsnr;
+        ek.rvalid = nvalid;
+        for (int s0 = 0; s0 < nsnr; s0 += chunk) {
+            b.snr0 = s0;
+            b.U = R * std::min(chunk, nsnr - s0);
+            {
+                Timed t(ctx, "rx_front");
+                (void)launch_rx_front(ctx->stream, ctx->op, s.k, ctx->ch, ctx->d_pn, seed, rep0, b);
+            }
+            ek.U = b.U;
+            ek.snr0 = s0;
+            // the per-realisation fields (h, xp, sym) go out with the first chunk
+            for (int f = 0; f < 6; ++f)
+                ek.tiles[f] = dst[f] && (f < 3 || s0 == 0) ? (flen[f] + EXPORT_TILE - 1) / EXPORT_TILE : 0;
+            {
+                Timed t(ctx, "k_export");
+                launch_export(ctx->stream, ek, f32);
+            }
+        }
+        DSCE_HIP_CHECK(hipGetLastError());
+        if (!to_device)
+            for (int f = 0; f < 6; ++f)
+                if (dst[f])
+                    DSCE_HIP_CHECK(hipMemcpyAsync((char*)dst[f] + (size_t)done * per_rep[f] * esz[f], ek.out[f],
+                                                  (size_t)nvalid * per_rep[f] * esz[f], hipMemcpyDeviceToHost,
+                                                  ctx->stream));
+        done += (uint64_t)nvalid;
+    }
+    DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (ctx->timing) collect_timing(ctx);
     API_END
 }
 

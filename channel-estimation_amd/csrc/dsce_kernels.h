@@ -238,6 +238,32 @@ unsigned launch_perfect_chain(hipStream_t s, const Opts& op, const SchemeK& sk, 
                               const PerfectDetectArgs* pd, int niter, bool stage0 = false);
 void launch_mmse_onetap(hipStream_t s, int LK, int NP, const double2* wd, const double2* hp, int n, double2* h);
 
+// Bulk export of one batch and SNR chunk after launch_rx_front (k_export,
+// kernels_export.hip; dsce_export): LS pilot estimates, the stage-0 one-tap
+// estimate Wd hP and the transpose of every requested field from the element-
+// major batch buffers to realisation-major outputs.  Fields in the order
+// y, hp_ls, h_est, h, xp, sym; tiles[f] = 32-element tiles of field f this
+// call writes (0: not requested, or a per-realisation field of a later SNR
+// chunk).  Output element of realisation rl (< rvalid; padding realisations are
+// written nowhere), SNR index snr: ((row0 + rl) nsnr + snr) len + element for
+// the per-unit fields y / hp_ls / h_est, (row0 + rl) len + element for h / xp / sym.
+constexpr int EXPORT_TILE = 32;
+struct ExportK {
+    const double2* y;         // [LK][U]
+    const double2* h;         // [LK][R]
+    const double2* xp;        // [NP][R]
+    const uint16_t* sidx;     // [ND][R]
+    const double2* wd;        // [snr][LK][NP]: diag(W) of variant 0 or the interpolation matrix (h_est only)
+    double2* hp;              // [NP][U] scratch: the LS estimates, written by the LS tiles, read by the h_est tiles
+    const int* pilot_pos;     // NP
+    double inv_sqrt_kappa;
+    int LK, NP, ND, R, U, snr0, nsnr, rvalid;
+    long long row0;           // output row of the batch's realisation 0
+    void* out[6];             // device destinations (complex128, or complex64 with f32; sym int32)
+    int tiles[6];
+};
+void launch_export(hipStream_t s, const ExportK& a, bool f32);
+
 // setup (correlation matrices and MMSE estimator)
 struct SetupArgs {
     int N, LK, NP, Nsym, ntap, nsnr;

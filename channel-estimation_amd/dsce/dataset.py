@@ -1,0 +1,141 @@
+"""Labelled channel-estimation data in bulk: per realisation the received grid
+y = Q'r, the LS pilot estimates, the MMSE one-tap estimate, the true one-tap
+channel h = diag(Q'HG), the pilots and the transmitted data symbols, written by
+the engine's export kernel (dsce_export) into NPZ shards:
+
+    python -m dsce.dataset --config default --scheme ofdm --snr-db 10 20 30 --seed 1 \\
+           --first-rep 0 --reps 65536 --shard-reps 8192 --dtype complex64 --out data/ofdm
+
+writes data/ofdm-00000.npz, data/ofdm-00001.npz, ...  A set is addressed by
+(seed, first_rep): realisation `rep` of a shard is realisation `rep` of
+dsce.simulate with the same seed, so any shard can be regenerated exactly.
+dsce.dataset.load(prefix) concatenates the shards.
+
+Arrays of a shard (n = realisations of the shard): y, hp_ls, h_est
+[n][n_snr][LK | NP], h [n][LK], xp [n][NP] (complex64 or complex128), sym
+[n][ND] int32; metadata: config, scheme, snr_db, pn_time, seed, first_rep,
+n_rep, dtype, pilot_pos, data_pos, symbols (the constellation), kappa, data_div,
+L, K, abi."""
+from __future__ import annotations
+
+import argparse
+import glob
+import os
+import sys
+
+import numpy as np
+
+DTYPES = ("complex64", "complex128")
+FIELDS = ("y", "hp_ls", "h_est", "h", "xp", "sym")
+
+
+def shard_path(prefix, index):
+    return "%s-%05d.npz" % (prefix, index)
+
+
+def shard_ranges(first_rep, n_rep, shard_reps):
+    """[(first, count)] of the shards of [first_rep, first_rep + n_rep): whole
+    shards of shard_reps realisations and one ragged last shard."""
+    if n_rep < 0 or shard_reps < 1:
+        raise ValueError("n_rep must be >= 0 and shard_reps >= 1")
+    return [(first_rep + o, min(shard_reps, n_rep - o)) for o in range(0, n_rep, shard_reps)]
+
+
+def write_shard(path, arrays, meta):
+    """One shard: the exported arrays plus the metadata, atomically (a temporary
+    file, then os.replace).  meta must carry first_rep and n_rep."""
+    n = int(meta["n_rep"])
+    for k, a in arrays.items():
+        if k not in FIELDS:
+            raise ValueError("unknown field %r" % k)
+        if a.shape[0] != n:
+            raise ValueError("field %s holds %d realisations, the shard %d" % (k, a.shape[0], n))
+    clash = set(arrays) & set(meta)
+    if clash:
+        raise ValueError("metadata keys shadow fields: %s" % sorted(clash))
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    tmp = path + ".tmp.npz"
+    np.savez(tmp, fields=np.array(sorted(arrays)), **arrays, **{k: np.asarray(v) for k, v in meta.items()})
+    os.replace(tmp, path)
+    return path
+
+
+def read_shard(path):
+    """(arrays, meta) of one shard."""
+    with np.load(path, allow_pickle=False) as z:
+        names = [str(f) for f in z["fields"]]
+        arrays = {k: z[k] for k in names}
+        meta = {k: (z[k].item() if z[k].ndim == 0 else z[k]) for k in z.files if k not in names and k != "fields"}
+    return arrays, meta
+
+
+def load(prefix):
+    """Every shard prefix-NNNNN.npz in order, concatenated over realisations:
+    (arrays, meta) with meta of the first shard and n_rep the total.  The
+    shards must be contiguous in the realisation index."""
+    paths = sorted(glob.glob(glob.escape(prefix) + "-[0-9][0-9][0-9][0-9][0-9].npz"))
+    if not paths:
+        raise FileNotFoundError("no shards %s-NNNNN.npz" % prefix)
+    parts, meta, nxt = [], None, None
+    for p in paths:
+        a, m = read_shard(p)
+        if meta is None:
+            meta = dict(m)
+        elif int(m["first_rep"]) != nxt or int(m["seed"]) != int(meta["seed"]) or sorted(a) != sorted(parts[0]):
+            raise ValueError("shard %s does not continue the set (first_rep %d, expected %d)"
+                             % (p, int(m["first_rep"]), nxt))
+        nxt = int(m["first_rep"]) + int(m["n_rep"])
+        parts.append(a)
+    arrays = {k: np.concatenate([a[k] for a in parts], axis=0) for k in parts[0]}
+    meta["n_rep"] = nxt - int(meta["first_rep"])
+    return arrays, meta
+
+
+def parser():
+    ap = argparse.ArgumentParser(prog="python -m dsce.dataset", description=__doc__.splitlines()[0])
+    ap.add_argument("--config", default="default", help="default (C2-C4) | c5 | paper")
+    ap.add_argument("--scheme", default="ofdm", choices=("ofdm", "fbmc_aux", "fbmc_cod"))
+    ap.add_argument("--snr-db", type=float, nargs="+", default=None, help="SNR points (default: the config's)")
+    ap.add_argument("--seed", type=int, default=0x5EED0000)
+    ap.add_argument("--first-rep", type=int, default=0)
+    ap.add_argument("--reps", type=int, required=True, help="realisations (any count)")
+    ap.add_argument("--shard-reps", type=int, default=8192, help="realisations per shard file")
+    ap.add_argument("--batch", type=int, default=8192, help="realisations per device batch")
+    ap.add_argument("--dtype", choices=DTYPES, default="complex64")
+    ap.add_argument("--no-mmse", action="store_true", help="skip dsce_build_mmse and the h_est field")
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--out", required=True, help="shard prefix: writes PREFIX-00000.npz ...")
+    return ap
+
+
+def main(argv=None):
+    a = parser().parse_args(argv)
+    if a.reps < 1 or a.shard_reps < 1 or a.first_rep < 0:
+        raise SystemExit("--reps and --shard-reps must be >= 1, --first-rep >= 0")
+
+    from dsce.configs import build_setup
+    from dsce.engine import ABI_VERSION, build_engine, gpu_tx
+
+    S = build_setup(a.config, schemes=(a.scheme,), snr_db=a.snr_db, tx=gpu_tx(a.device))
+    sc = S.schemes[a.scheme]
+    eng = build_engine(S, device=a.device, batch=max(64, min(a.batch, a.reps)), mmse=not a.no_mmse)
+    fields = tuple(f for f in FIELDS if not (a.no_mmse and f == "h_est"))
+    base = dict(config=a.config, scheme=a.scheme, snr_db=np.asarray(S.snr_db, dtype=float),
+                pn_time=np.asarray(S.pn_time, dtype=float), seed=int(a.seed), dtype=a.dtype,
+                pilot_pos=np.asarray(sc.pilot_pos, dtype=np.int32), data_pos=np.asarray(sc.data_pos, dtype=np.int32),
+                symbols=np.asarray(sc.const.SymbolMapping, dtype=np.complex128).ravel(), kappa=float(sc.kappa),
+                data_div=float(sc.data_div), L=int(S.L), K=int(sc.LK // S.L), abi=int(ABI_VERSION))
+    try:
+        for i, (first, n) in enumerate(shard_ranges(a.first_rep, a.reps, a.shard_reps)):
+            arrays = eng.export(0, a.seed, first, n, fields=fields, dtype=np.dtype(a.dtype))
+            print("wrote", write_shard(shard_path(a.out, i), arrays, dict(base, first_rep=int(first), n_rep=int(n))),
+                  flush=True)
+    finally:
+        eng.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

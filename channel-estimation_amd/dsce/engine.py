@@ -24,10 +24,16 @@ EXPORTED = [
     "dsce_set_noise_slot", "dsce_set_interpolation", "dsce_enable_mse", "dsce_get_mse", "dsce_trace_unit_ex",
     "dsce_scheme_dims", "dsce_path_info", "dsce_set_option", "dsce_get_option", "dsce_fp64_mfma_peak",
     "dsce_kernel_work", "dsce_structured_check", "dsce_create_multi", "dsce_group_info",
-    "dsce_transmission_matrix", "dsce_jakes_info",
+    "dsce_transmission_matrix", "dsce_jakes_info", "dsce_export",
 ]
 
-ABI_VERSION = 8
+ABI_VERSION = 9
+
+# dsce_export flags (include/dsce.h DSCE_EXPORT_*)
+EXPORT_F32 = 1 << 0
+EXPORT_DEVICE = 1 << 1
+# dsce_export fields in the order of dsce_export_out
+EXPORT_FIELDS = ("y", "hp_ls", "h_est", "h", "xp", "sym")
 
 # dsce_jakes_info kernels (include/dsce.h DSCE_JAKES_*)
 JAKES_KERNELS = {0: "none", 1: "static", 2: "discrete", 3: "full", 4: "win_rec", 5: "win_mom", 6: "win_grp"}
@@ -72,6 +78,11 @@ class Trace(C.Structure):
                 ("hp_stages", C.POINTER(C.c_double)), ("hest_stages", C.POINTER(C.c_double)),
                 ("yest_stages", C.POINTER(C.c_double)), ("yperf_stages", C.POINTER(C.c_double)),
                 ("dec_est", C.POINTER(C.c_int32)), ("dec_perf", C.POINTER(C.c_int32))]
+
+
+class ExportOut(C.Structure):
+    _fields_ = [("y", C.c_void_p), ("hp_ls", C.c_void_p), ("h_est", C.c_void_p), ("h", C.c_void_p),
+                ("xp", C.c_void_p), ("sym", C.POINTER(C.c_int32))]
 
 
 class TxDesc(C.Structure):
@@ -137,6 +148,7 @@ def load_library(path=None):
     lib.dsce_fp64_mfma_peak.argtypes = [vp, dp]
     lib.dsce_kernel_work.argtypes = [vp, C.c_char_p, dp, dp]
     lib.dsce_structured_check.argtypes = [vp, C.c_int32, dp]
+    lib.dsce_export.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(ExportOut)]
     for name in EXPORTED:
         fn = getattr(lib, name)
         if name != "dsce_last_error":
@@ -359,6 +371,69 @@ class Engine:
                     hest=v(bufs["hest"]).reshape(ns, LK), yest=v(bufs["yest"]).reshape(ns, LK),
                     yperf=v(bufs["yperf"]).reshape(ns, LK), dec_e=dec_e.reshape(ns, ND), dec_p=dec_p.reshape(ns, ND))
 
+    # -- bulk export (ABI 9) ---------------------------------------------------
+    def export_shapes(self, sid, n_rep):
+        """Shapes of dsce_export's arrays for n_rep realisations of scheme sid."""
+        d = self.scheme_dims(sid)
+        n = int(n_rep)
+        return dict(y=(n, d.n_snr, d.lk), hp_ls=(n, d.n_snr, d.n_pilots), h_est=(n, d.n_snr, d.lk), h=(n, d.lk),
+                    xp=(n, d.n_pilots), sym=(n, d.n_data))
+
+    def _export(self, sid, seed, first_rep, n_rep, flags, ptrs):
+        bad = [f for f in ptrs if f not in EXPORT_FIELDS]
+        if bad:
+            raise ValueError("unknown export field(s) %s (of %s)" % (bad, list(EXPORT_FIELDS)))
+        o = ExportOut()
+        for f, p in ptrs.items():
+            setattr(o, f, C.cast(p, C.POINTER(C.c_int32)) if f == "sym" else p)
+        self._chk(self.lib.dsce_export(self.h, int(sid), int(seed), int(first_rep), int(n_rep), int(flags),
+                                       C.byref(o)), "dsce_export")
+
+    def export(self, sid, seed, first_rep, n_rep, fields=EXPORT_FIELDS, dtype=np.complex128):
+        """Per-realisation data of realisations [first_rep, first_rep + n_rep) of
+        scheme sid (dsce_export) as a dict of NumPy arrays: y, hp_ls, h_est
+        [n_rep][n_snr][LK | NP], h [n_rep][LK], xp [n_rep][NP] (dtype complex128,
+        or complex64: DSCE_EXPORT_F32) and sym [n_rep][ND] int32.  Realisation
+        rep is realisation rep of run() with the same seed."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.complex128), np.dtype(np.complex64)):
+            raise ValueError("export dtype must be complex128 or complex64")
+        shapes = self.export_shapes(sid, n_rep)
+        out = {f: np.zeros(shapes[f], dtype=np.int32 if f == "sym" else dt) for f in fields}
+        self._export(sid, seed, first_rep, n_rep, EXPORT_F32 if dt == np.dtype(np.complex64) else 0,
+                     {f: a.ctypes.data for f, a in out.items()})
+        return out
+
+    def export_torch(self, sid, seed, first_rep, n_rep, fields=EXPORT_FIELDS, dtype=None, device=None):
+        """export() into torch tensors on the context's GPU, written by the export
+        kernel itself (DSCE_EXPORT_DEVICE): no host copy.  dtype torch.complex128
+        (default) or torch.complex64; sym is torch.int32.  device: the HIP device
+        of the context (default: member 0 of group_info()).
+
+        torch and the engine must share one HIP runtime for a pointer of one to
+        mean anything to the other.  A torch wheel that bundles its runtime gets
+        that when torch is imported before the engine's library is loaded
+        (libdsce.so then binds to the runtime torch loaded, like bench.py and
+        dsce.simulate under a launcher); the other order leaves torch without a
+        usable device, which is reported here."""
+        import torch
+        dtype = torch.complex128 if dtype is None else dtype
+        if dtype not in (torch.complex128, torch.complex64):
+            raise ValueError("export_torch dtype must be torch.complex128 or torch.complex64")
+        if not torch.cuda.is_available():
+            raise DsceError("export_torch: torch sees no HIP device in this process; import torch before the "
+                            "first dsce.engine.Engine is created so that both use one HIP runtime")
+        if device is None:
+            device = self.group_info()[0][0]
+        shapes = self.export_shapes(sid, n_rep)
+        dev = "cuda:%d" % int(device)
+        out = {f: torch.empty(shapes[f], dtype=torch.int32 if f == "sym" else dtype, device=dev) for f in fields}
+        # the allocations (and any work torch queued on them) precede the engine's stream
+        torch.cuda.current_stream(dev).synchronize()
+        self._export(sid, seed, first_rep, n_rep, EXPORT_DEVICE | (EXPORT_F32 if dtype == torch.complex64 else 0),
+                     {f: t.data_ptr() for f, t in out.items()})
+        return out
+
     # -- engine state ------------------------------------------------------------
     def scheme_dims(self, sid):
         d = Dims()
@@ -485,9 +560,11 @@ def gpu_tx(device=0):
     return produce
 
 
-def build_engine(setup, schemes=None, device=0, zero_threshold=None, batch=None, options=None):
+def build_engine(setup, schemes=None, device=0, zero_threshold=None, batch=None, options=None, mmse=True):
     """Engine configured like the script: channel, SNR list, schemes, MMSE setup.
-    ``options``: dsce_set_option name -> value, applied before the MMSE build."""
+    ``options``: dsce_set_option name -> value, applied before the MMSE build.
+    ``mmse=False`` leaves dsce_build_mmse out (enough for the probes and for
+    export() without h_est)."""
     eng = Engine(device)
     for k, v in (options or {}).items():
         eng.set_option(k, v)
@@ -496,7 +573,8 @@ def build_engine(setup, schemes=None, device=0, zero_threshold=None, batch=None,
     names = list(setup.schemes) if schemes is None else list(schemes)
     for n in names:
         eng.add_scheme(setup.schemes[n])
-    eng.build_mmse(setup.zero_threshold if zero_threshold is None else zero_threshold)
+    if mmse:
+        eng.build_mmse(setup.zero_threshold if zero_threshold is None else zero_threshold)
     if batch:
         eng.set_batch(batch)
     return eng

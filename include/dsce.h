@@ -29,6 +29,9 @@
  *                            'linear'/'nearest'/'FullAverage'/'MovingBlockAverage'
  *                            (PSACE.m:73-107, :115-133) as its LK x NP weight matrix
  *   dsce_set_noise_slot   <- separate n_FBMC / n_OFDM draws     SimpleVersion_DoublyFlat.m:125-126
+ *   dsce_export           <- the workspace arrays of the loop body, per realisation:
+ *                            y, hP_LS, h_hat (stage 0), h, xP and the data symbols
+ *                                                               script:355-368, :388-393, :406-428
  *
  * Conventions
  *  - Return 0 on success, a negative DSCE_E* code on failure; the message is
@@ -69,6 +72,9 @@
  *   [n_schemes][2 csi: 0 = MMSE estimate, 1 = perfect CSI][2 edge: 0 = all bits,
  *    1 = no-edge bits][n_snr][1 + n_iter stages: 0 = one-tap, i = IC iteration i]
  * (C order, last index fastest).  BER = count / bits, bits from dsce_bits_per_rep.
+ *
+ * ABI 9 adds dsce_export (dsce_export_out, DSCE_EXPORT_*): per-realisation data
+ * in bulk.  Every ABI 8 entry point is unchanged.
  */
 #ifndef DSCE_H
 #define DSCE_H
@@ -79,7 +85,7 @@
 extern "C" {
 #endif
 
-#define DSCE_ABI_VERSION 8
+#define DSCE_ABI_VERSION 9
 
 #define DSCE_OK 0
 #define DSCE_EINVAL -1      /* bad argument / shape */
@@ -261,7 +267,9 @@ const char* dsce_last_error(const dsce_ctx* ctx);
  *    streams are keyed by the global realisation index, so the counts equal a
  *    single context's bit for bit for any member count.
  *  - Every other call (probes, queries, dsce_kernel_time: member 0's own
- *    launches, i.e. its slice) uses member 0.
+ *    launches, i.e. its slice) uses member 0.  dsce_export too: the whole range
+ *    is simulated and written by member 0 (DSCE_EXPORT_DEVICE pointers are
+ *    memory of devices[0]).
  * dsce_destroy on the handle frees every member and communicator. */
 int dsce_create_multi(const int32_t* devices, int32_t n_devices, dsce_ctx** out);
 /* Members of a context: *n_devices, their HIP devices (optional, n_devices
@@ -353,6 +361,40 @@ int dsce_get_mse(dsce_ctx* ctx, double* err_sum, double* pow_sum);
  * (rep, snr) unit returned through `out` (see dsce_trace). */
 int dsce_trace_unit_ex(dsce_ctx* ctx, int32_t scheme_id, uint64_t seed, uint64_t rep, int32_t snr_index,
                        const dsce_trace* out);
+
+/* ---- bulk export (ABI 9) ------------------------------------------------ */
+#define DSCE_EXPORT_F32     (1u << 0)  /* complex64 / float outputs instead of complex128 */
+#define DSCE_EXPORT_DEVICE  (1u << 1)  /* every non-null pointer is device memory on the context's GPU */
+
+typedef struct {               /* every pointer optional; realisation-major, C order, element fastest */
+    void*    y;        /* [n_rep][n_snr][LK]  y = Q'r                      script:406-409 */
+    void*    hp_ls;    /* [n_rep][n_snr][NP]  LS pilot estimates           script:412-414 */
+    void*    h_est;    /* [n_rep][n_snr][LK]  diag(D_hat), stage 0: W (variant 0) or the
+                          interpolation matrix of dsce_set_interpolation   script:417-428 */
+    void*    h;        /* [n_rep][LK]         diag(D), perfect CSI         script:388-393 */
+    void*    xp;       /* [n_rep][NP]         unit-modulus pilots          script:365-368 */
+    int32_t* sym;      /* [n_rep][ND]         transmitted data symbol index (bi2de of the BITS stream) */
+} dsce_export_out;
+
+/* Realisations [first_rep, first_rep + n_rep) of one scheme, every SNR point, as
+ * the arrays of dsce_export_out: the Philox streams and the Jakes / TX /
+ * receiver-front kernels of dsce_run with the context's options, so realisation
+ * `rep` of an export is realisation `rep` of a run with the same seed.  The
+ * export stops after the receiver front: no IC stage, no perfect-CSI chain, and
+ * nothing is added to the error counters, the MSE sums or dsce_path_info.
+ * Works batch by batch (dsce_set_batch) and SNR chunk by SNR chunk (option
+ * snr_chunk); the padding realisations of a tail wave are written nowhere.  Any
+ * n_rep >= 0.  Synchronous.  Complex outputs are interleaved (re, im) doubles,
+ * or floats with DSCE_EXPORT_F32 (each fp64 value rounded once, to nearest, at
+ * the store).  Host destinations go through a device staging buffer of one
+ * batch; with DSCE_EXPORT_DEVICE the kernel writes the caller's device memory.
+ * DSCE_ESTATE before channel, SNR points or scheme are set, and for h_est
+ * without a built W (dsce_build_mmse) or an interpolation matrix — the other
+ * fields need neither.  DSCE_EINVAL for a null out, no field requested, an
+ * unknown flag, or DSCE_EXPORT_DEVICE with a pointer that is not device memory
+ * of the context's GPU.  With dsce_enable_timing the kernel is "k_export". */
+int dsce_export(dsce_ctx* ctx, int32_t scheme_id, uint64_t seed, uint64_t first_rep, uint64_t n_rep,
+                uint32_t flags, const dsce_export_out* out);
 
 /* ---- engine state ------------------------------------------------------- */
 int dsce_scheme_dims(dsce_ctx* ctx, int32_t scheme_id, dsce_dims* dims);
