@@ -10,7 +10,7 @@ INC := -I$(ROOT)/../include -I$(ROOT)/csrc
 FLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -ffp-contract=off -Wall -Wno-unused-result
 ASAN_FLAGS := -Xarch_host -fsanitize=address -Xarch_host -fno-omit-frame-pointer
 LIBS := -L/opt/rocm/lib -lrccl -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
-HDR := $(ROOT)/csrc/dsce_common.h $(ROOT)/csrc/dsce_kernels.h $(ROOT)/../include/dsce.h
+include $(ROOT)/kernels.mk
 ASAN_DIR := $(ROOT)/build/asan
 ASAN_BIN := $(ROOT)/../tools/asan/dsce_asan_driver
 
@@ -24,8 +24,7 @@ $(ASAN_DIR)/asan_driver.o: $(ROOT)/../tools/asan/asan_driver.cpp $(ROOT)/../incl
 	@mkdir -p $(ASAN_DIR)
 	$(HIPCC) $(FLAGS) $(ASAN_FLAGS) $(INC) -c $< -o $@
 
-$(ASAN_BIN): $(ASAN_DIR)/asan_driver.o $(ASAN_DIR)/dsce_api.o $(ROOT)/build/kernels_mc.o $(ROOT)/build/kernels_setup.o \
-             $(ROOT)/build/kernels_export.o
+$(ASAN_BIN): $(ASAN_DIR)/asan_driver.o $(ASAN_DIR)/dsce_api.o $(KERNEL_OBJ)
 	$(HIPCC) $(FLAGS) $(ASAN_FLAGS) $^ -o $@ $(LIBS)
 
 clean:

@@ -445,7 +445,7 @@ void build_chain_tables(dsce_ctx* c, Scheme& s, const std::vector<int>& grid, co
     const int LK = s.LK, NP = s.d.n_pilots, M = s.d.mod_order;
     const double2 scale = k.pf_scale;
     const double cs = (1.0 / k.data_div) * k.slI;             // chain_detect's scI
-    std::vector<double2> symc(256), sym(256), amt(192), twa(48), rpv, wrow;
+    std::vector<double2> symc(256), sym(256), amt(192), rpv, wrow;
     std::vector<int> rdc, rpc;
     for (int t = 0; t < 256; ++t) {
         const double2 a = t < M ? s.symbols[t] : make_double2(0.0, 0.0);
@@ -465,10 +465,6 @@ void build_chain_tables(dsce_ctx* c, Scheme& s, const std::vector<int>& grid, co
         const int dir = t / 96, m = (t / 16) % 6, ii = t & 3, kk = (t >> 2) & 3;
         const double2 v = w24_signed((6 * ii * kk + (dir ? ii : kk) * m) % 24);
         amt[t] = dir ? c_mul(scale, make_double2(v.x, -v.y)) : v;
-    }
-    for (int t = 0; t < 48; ++t) {                              // twa[dir][r][m']
-        const double2 v = w24_signed(((t / 6) % 4) * (t % 6));
-        twa[t] = t >= 24 ? c_mul(scale, make_double2(v.x, -v.y)) : v;
     }
     std::vector<unsigned> gw(64, 0u);
     for (int t = 0; t < 256; ++t) {
@@ -490,7 +486,6 @@ void build_chain_tables(dsce_ctx* c, Scheme& s, const std::vector<int>& grid, co
     k.ct_symc = dupload(c, symc);
     k.ct_sym = dupload(c, sym);
     k.ct_amt = dupload(c, amt);
-    k.ct_twa = dupload(c, twa);
     k.ct_grid = dupload(c, gw);
     k.ct_rpv = dupload(c, rpv);
     k.ct_rdc = dupload(c, rdc);
@@ -1630,7 +1625,7 @@ void run_batch(dsce_ctx* c, uint64_t seed, uint64_t rep0, int R, int nvalid, Tra
                 PerfectDetectArgs pd{c->d_counters, (int)si, 0, c->niter + 1, c->nsnr, 0, s.k.slI, s.k.slQ};
                 // the low-rank tap operator (both passes or neither: the data pass
                 // reads the pilot pass's Z instead of its LS pilots)
-                const bool lr = op.mic_lr && (op.mic_net & 1) && s.Bz;
+                const bool lr = op.mic_lr && s.Bz;
                 // (r06: the r05 options ic_streams 2 / 3 — the chain on a second
                 // stream, or beside the pilot pass in one launch, k_ic_pair — were
                 // within box noise and are retired; "ic_stages" spans the group)
@@ -1642,13 +1637,11 @@ void run_batch(dsce_ctx* c, uint64_t seed, uint64_t rep0, int R, int nvalid, Tra
                     }
                     {
                         Timed t(c, "k_mic_pilot");
-                        s.path |= launch_mmse_stages(c->stream, s.k, mm, c->ch, b, &pd, c->niter, op.xcd, 1,
-                                                     (op.mic_net & 2) != 0, lr);
+                        s.path |= launch_mmse_stages(c->stream, s.k, mm, c->ch, b, &pd, c->niter, op.xcd, 1, lr);
                     }
                     {
                         Timed t(c, "k_mic_data");
-                        s.path |= launch_mmse_stages(c->stream, s.k, mm, c->ch, b, &pd, c->niter, op.xcd, 2,
-                                                     (op.mic_net & 1) != 0, lr);
+                        s.path |= launch_mmse_stages(c->stream, s.k, mm, c->ch, b, &pd, c->niter, op.xcd, 2, lr);
                     }
                 }
                 if (to && to->hp_stages)
@@ -3040,8 +3033,8 @@ int dsce_fp64_mfma_peak(dsce_ctx* ctx, double* tflops) {
 
 // Kernel-selection options (Opts); the defaults are the measured-best path.
 #define DSCE_OPTIONS(X)                                                                                  \
-    X(xcd) X(fuse_stage) X(pic_chain) X(pfuse) X(stage_split) X(stage_rb) X(noise_fuse) \
-    X(snr_chunk) X(jakes_rpw) X(wtrim) X(wcontract_valu) X(mmse_ic) X(jakes_win) X(txrx_fft) X(snr_base) X(jakes_mom) X(realise_win) X(tx_rows) X(pic_net) X(mic_net) X(mic_lr) X(pic_poly) X(wrow) X(jakes_grp2)
+    X(xcd) X(fuse_stage) X(pic_chain) X(pfuse) X(stage_split) X(noise_fuse) \
+    X(snr_chunk) X(jakes_rpw) X(wtrim) X(wcontract_valu) X(mmse_ic) X(jakes_win) X(txrx_fft) X(snr_base) X(jakes_mom) X(realise_win) X(tx_rows) X(mic_lr) X(pic_poly) X(jakes_grp2)
 
 static int set_option_one(dsce_ctx* ctx, const char* name, int64_t value) {
     API_BEGIN
@@ -3054,8 +3047,10 @@ static int set_option_one(dsce_ctx* ctx, const char* name, int64_t value) {
 #undef X
     if (!slot && (n == "pic_skip" || n == "ic_streams"))
         throw ApiError(DSCE_EINVAL, "option '" + n + "' was retired in r06 (measured neutral in r04 / r05; DESIGN.md 2.0d, 2.0f)");
+    if (!slot && (n == "pic_net" || n == "mic_net" || n == "stage_rb" || n == "wrow"))
+        throw ApiError(DSCE_EINVAL, "option '" + n + "' was retired: no scheme or channel selected its other values "
+                                    "(DESIGN.md 2.0, Pruned after r06)");
     if (!slot) throw ApiError(DSCE_EINVAL, "unknown option '" + n + "'");
-    if (n == "stage_rb" && value != 4 && value != 8 && value != 16) throw ApiError(DSCE_EINVAL, "stage_rb: 4 | 8 | 16");
     if (n == "jakes_rpw" && value != 1 && value != 2) throw ApiError(DSCE_EINVAL, "jakes_rpw: 1 | 2");
     if (n == "pic_chain" && value != 0 && value != 3)
         throw ApiError(DSCE_EINVAL, "pic_chain: 0 (per-iteration passes) | 3 (k_pic_fft); the r01 chains 1 / 2 "

@@ -205,7 +205,6 @@ struct SchemeK {
     const double2* ct_symc;       // [256] stage_sym(symbol) * scI (k_pic_fft); 0 past M
     const double2* ct_sym;        // [256] stage_sym(symbol) (k_mic_pilot / k_mic_data); 0 past M
     const double2* ct_amt;        // [2][6][16] the matrix-core network's A_m (flat = the LDS order)
-    const double2* ct_twa;        // [2][4][6] the DPP network's lane twiddles (flat = the LDS order)
     const unsigned* ct_grid;      // [64] slice6's byte grid [iI][iQ] (row stride 16) as words
     const double2* ct_rpv;        // [QH blk][24] row precoder value
     const int* ct_rdc;            // [QH blk][24] data index << 1 | no-edge, or -1

@@ -15,7 +15,6 @@ struct Opts {
     int pic_chain = 3;        // perfect-CSI IC: 0 per-iteration passes, 1 VALU chain, 2 MFMA chain, 3 FFT chain
     int pfuse = 1;            // perfect-CSI detection fused into the second banded pass
     int stage_split = 0;      // 1: 3-kernel stage (k_ls_hest, k_detect, k_precode) for every scheme
-    int stage_rb = 8;         // rows per wave of k_stage_fused: 4 | 8 | 16
     int noise_fuse = 1;       // AWGN drawn inside the Q^H pass (disjoint Q^H blocks)
     int snr_chunk = 0;        // SNR points per receiver chunk (0: all)
     int jakes_rpw = 2;        // realisations per Jakes wave (1 | 2)
@@ -26,10 +25,6 @@ struct Opts {
     int txrx_fft = 1;         // TX + channel + receiver front of FFT-form OFDM in one pass (k_txrx_fft)
     int snr_base = 0;         // noise sub-stream of SNR index k is snr_base + k (SNR-sharded sweeps)
     int tx_rows = 1;          // row-local precoders: TX symbols drawn row-parallel (k_tx_rows)
-    int pic_net = 1;          // k_pic_fft's 4-point network: 1 = v_mfma_f64_4x4x4 (quarters on 16-lane rows), 0 = DPP
-    int mic_net = 3;          // the same network for k_mic_data (bit 0) / k_mic_pilot (bit 1), whose tap GEMM then
-                              // needs no exchange: data 3.99 -> 3.65 ms, pilot 1.91 -> 2.00 ms (237 VGPRs, r03: 1);
-                              // with the low-rank taps the pilot kernel gains too: 1.625 -> 1.576 ms (r04: 3)
     int realise_win = 0;      // dsce_channel_realise forms only the JakesChunks samples (tests the window kernels)
     int mic_lr = 1;           // MMSE IC taps in the low-rank form T_k Z (k_mic_pilot / k_mic_data) where
                               // build_mic_lr verified it; 0 = the tap GEMM Bv hP on the matrix cores
@@ -37,8 +32,6 @@ struct Opts {
                               // L != 24) as IDFT-L per symbol + window sums per residue + DFT-L per symbol
                               // (k_poly_syn / k_poly_chan / k_poly_ana) instead of the two banded passes
                               // (r04 box, C3: 14.3 -> 8.7 ms per iteration); 0 = the banded passes
-    int wrow = 1;             // unfused W contraction of 32-row blocks (FBMC, C5) as one GEMM per row tile
-                              // (k_wrow3: X = hP v_c as the B operand, no per-tile epilogue); 0 = k_wpair3
     int jakes_grp2 = 1;       // two-tap channels: k_jakes_grp2 (both taps per wave, each Philox block drawn
                               // once, LG = 16 / anchor groups); 0 = k_jakes_grp per tap
     int jakes_mom = 2;        // Jakes taps of the read windows: 2 = Taylor anchors over groups of windows
@@ -227,7 +220,7 @@ bool mmse_stages_ok(const Opts& op, const SchemeK& sk, const MmseK& mm, const Ch
                     int niter);
 // part: 1 = k_mic_pilot, 2 = k_mic_data (the data kernel reads the pilot kernel's hpa)
 unsigned launch_mmse_stages(hipStream_t s, const SchemeK& sk, const MmseK& mm, const ChannelK& ch, McBuffers& b,
-                            const PerfectDetectArgs* pd, int niter, int xcd, int part, bool nm = true, bool lr = false);
+                            const PerfectDetectArgs* pd, int niter, int xcd, int part, bool lr = false);
 unsigned launch_perfect_ic(hipStream_t s, const Opts& op, const SchemeK& sk, const ChannelK& ch, McBuffers& b,
                            const PerfectDetectArgs* pd);
 // The whole perfect-CSI IC chain (iterations 1..niter) in one kernel, u in

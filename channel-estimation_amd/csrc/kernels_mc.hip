@@ -229,7 +229,7 @@ __device__ __forceinline__ double2 c_mul_fma(double2 z, double2 w) {
     return make_double2(fma(z.x, w.x, -z.y * w.y), fma(z.x, w.y, z.y * w.x));
 }
 
-// DPP move of a double / complex within each quad of lanes (quad_perm control;
+// DPP move of a double within each quad of lanes (quad_perm control;
 // also the row controls: 0x141 row_half_mirror, 0x128 row_ror 8)
 template <int CTRL>
 __device__ __forceinline__ double dpp_d(double v) {
@@ -237,11 +237,8 @@ __device__ __forceinline__ double dpp_d(double v) {
     return __hiloint2double(__builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, false),
                             __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, false));
 }
-template <int CTRL>
-__device__ __forceinline__ double2 dpp_c(double2 v) { return make_double2(dpp_d<CTRL>(v.x), dpp_d<CTRL>(v.y)); }
 static constexpr int QP_XOR1 = 0xb1;    // quad_perm [1, 0, 3, 2]
 static constexpr int QP_XOR2 = 0x4e;    // quad_perm [2, 3, 0, 1]
-static constexpr int QP_PREV = 0x4b;    // quad_perm [3, 2, 0, 1]: the lane holding the previous time quarter
 
 static constexpr int JCH_MAX = 16;
 
@@ -1729,12 +1726,6 @@ __constant__ double2 kW24[12] = {
     {-0.86602540378443865, 0.5},
     {-0.96592582628906829, 0.25881904510252076}};
 
-// x * (c + S i s) for compile-time c, s
-template <int S>
-__device__ __forceinline__ double2 cmul_const(double2 x, double c, double s) {
-    return make_double2(fma(x.x, c, -(S * s) * x.y), fma(x.y, c, (S * s) * x.x));
-}
-
 // DFT-3 with sign S (S = +1: sum x[n] e^{+2 pi i nk/3}); the +-i H (b - c)
 // rotation fused into the output FMAs (12 FP64 ops)
 template <int S>
@@ -1750,15 +1741,6 @@ __device__ __forceinline__ void dft3(double2& a, double2& b, double2& c) {
 // a * b with two FMAs (2 mul + 2 fma instead of 4 mul + 2 add under -ffp-contract=off)
 __device__ __forceinline__ double2 c_mulf(double2 a, double2 b) {
     return make_double2(fma(a.x, b.x, -(a.y * b.y)), fma(a.x, b.y, a.y * b.x));
-}
-
-// e * w of the quad network's middle twiddle: 1 on lanes 0-2, +i (S = 1, forward)
-// or -i (S = -1, inverse) on lane 3 -- as selects (five 32-bit ops) instead of a
-// complex product (four f64 ops)
-template <int S>
-__device__ __forceinline__ double2 quad_tw(double2 e, bool r3) {
-    const double nx = S > 0 ? -e.y : e.y, ny = S > 0 ? e.x : -e.x;
-    return make_double2(r3 ? nx : e.x, r3 ? ny : e.y);
 }
 
 
@@ -1806,13 +1788,13 @@ __device__ __forceinline__ void dft6(double2 (&x)[6]) {
     }
 }
 
-// k_pic_fft: a lane QUAD owns a unit.  Lane r holds the rows 4a + r (a = 0..5)
-// — u (the decisions), the iteration-invariant y / h and 1 / h, and the channel
-// taps of its samples, all in registers, so the iteration loop reads no memory
-// — and, in the time domain, the samples 6c + m' with c = bitrev2(r).  DFT-24 =
-// DFT-6 per lane x a radix-2 x 2 network across the quad (DPP quad_perm), lane
-// twiddles w24^(r m') from LDS; the output scale qs gs is folded into the
-// forward twiddles.  One-tap z = y_perf / h = y / h - acc / h + u.
+// k_pic_fft: four lanes own a unit, one per 16-lane row (lane = 16 r + unit).
+// Lane r holds the rows 4a + r (a = 0..5) — u (the decisions), the
+// iteration-invariant y / h and 1 / h, and the channel taps of its samples, all
+// in registers, so the iteration loop reads no memory — and, in the time domain,
+// the samples 6r + m'.  DFT-24 = DFT-6 per lane x a 4-point network across the
+// unit's four lanes on the matrix cores (below); the output scale qs gs is
+// folded into the forward matrices.  One-tap z = y_perf / h = y / h - acc / h + u.
 // 198 VGPRs, 2 waves / SIMD (3 waves forced spills or per-iteration reloads of
 // y, h and the taps: 4.45 / 5.25 ms vs 2.57 ms per 65536-realisation launch).
 // Block = 256 threads = 64 units of one symbol; grid: symbols x units/64,
@@ -1821,8 +1803,8 @@ __device__ __forceinline__ void dft6(double2 (&x)[6]) {
 // perfect-CSI branch, the one-tap x = y ./ h (script:450-466), so no stage
 // kernel runs in front: u starts as P [xP; 0] (xs of the pilot rows) and the
 // data rows get the stage-0 decisions in registers.
-// NM (r03k): the 4-point network on the matrix cores instead.  A unit's four
-// quarters sit on the four 16-lane rows (lane = 16 r + unit), which is the K
+// The 4-point network (r03k; up to r06 a DPP quad network was kept as an option):
+// the unit's four quarters sit on the four 16-lane rows, which is the K
 // index of v_mfma_f64_4x4x4f64 (4 blocks of 4 units: B[k][n] in lane 16 k +
 // 4 c + n, D[i][n] in lane 16 i + 4 c + n, A[i][k] in lane 16 k + 4 c + i), so
 // per sample m the whole network including the lane twiddle is one complex
@@ -1845,16 +1827,15 @@ __device__ __forceinline__ void dft6(double2 (&x)[6]) {
 // constellation; the constant rows of u (pilots) are per-lane LDS slots read
 // through the same address select, so a row's new u is one LDS read.
 // (vb / vn = the block's index in the grid and the grid's size, vb % 8 = the XCD)
-template <int NT, int SH, bool TRACE, bool S0, bool NM>
+template <int NT, int SH, bool TRACE, bool S0>
 __device__ __forceinline__ void pic_fft_body(const SchemeK& sk, const BandOrder& ord, const double2* __restrict__ ir, int N,
                                              const StorePerfectDetect& o, int niter, int vb, int vn) {
     int ug, blk;
     band_block(ord, sk.QH.nblk, ug, blk, vb, vn);
-    const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, r = NM ? l >> 4 : l & 3;
+    const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, r = l >> 4;
     const int U = o.U, R = o.R;
-    const int unit = ug * WAVE + w * 16 + (NM ? (l & 15) : (l >> 2));
+    const int unit = ug * WAVE + w * 16 + (l & 15);
     const int rl = unit % R;
-    const int cq = NM ? r : (r >> 1) + 2 * (r & 1);            // time quarter of this lane
     const int row0 = sk.QH.row0[blk], klo = sk.QH.klo[blk];
     const double cs = o.scI, rq = o.rQ;                        // the chain's scale (host: scI != 0), scQ / scI
     __shared__ double2 sym[256];
@@ -1862,8 +1843,7 @@ __device__ __forceinline__ void pic_fft_body(const SchemeK& sk, const BandOrder&
     const unsigned char* sgrid = (const unsigned char*)sgridw;
     __shared__ double2 rpv[24];
     __shared__ int rdc[24];
-    __shared__ double2 twa[2][4][6];                            // [IFFT / FFT][lane r][m']
-    __shared__ double2 amt[NM ? 2 : 1][6][16];                  // NM: A_m[i][k] at [dir][m][i + 4 k]
+    __shared__ double2 amt[2][6][16];                          // A_m[i][k] at [dir][m][i + 4 k]
     __shared__ int cntl[4][PM_MAXIT + 1];                      // [wave][stage]
     __shared__ double2 ucst[6][256];                            // the lane's constant rows of u (scaled)
     // decisions u (scaled) and the iteration-invariant Yo and 1 / h of the lane's
@@ -1873,7 +1853,7 @@ __device__ __forceinline__ void pic_fft_body(const SchemeK& sk, const BandOrder&
     double2 taps[6][NT];
     const __amdgpu_buffer_rsrc_t trs =
         buf_rsrc(ir + (size_t)klo * R, ((size_t)(NT - 1) * N + (N - klo)) * R * sizeof(double2));
-    const unsigned tv0 = (unsigned)(6 * cq * R + rl) * 16u;
+    const unsigned tv0 = (unsigned)(6 * r * R + rl) * 16u;     // r is also the lane's time quarter
     {
         // table loads, then the per-unit loads (raw y and h into yh / hc), then
         // the LDS writes: the writes wait only for the tables (vmcnt retires in
@@ -1886,7 +1866,7 @@ __device__ __forceinline__ void pic_fft_body(const SchemeK& sk, const BandOrder&
         const int rt = min(tid, 23);
         const double2 pv = sk.ct_rpv[blk * 24 + rt];
         const int rdv = sk.ct_rdc[blk * 24 + rt];
-        const double2 nt = NM ? sk.ct_amt[min(tid, 191)] : sk.ct_twa[min(tid, 47)];
+        const double2 nt = sk.ct_amt[min(tid, 191)];
         const RowView vu = S0 ? RowView(o.xs, row0, R, r, rl, 16) : RowView(o.u, row0, U, r, unit, 16);
         const RowView vs(o.sidr, row0, R, r, rl, 2), vy(o.y, row0, U, r, unit, 16), vh(o.h, row0, R, r, rl, 16);
 #pragma unroll
@@ -1904,27 +1884,21 @@ __device__ __forceinline__ void pic_fft_body(const SchemeK& sk, const BandOrder&
         sgridw[min(tid, 63)] = gw;
         rpv[rt] = pv;
         rdc[rt] = rdv;
-        if (!NM) (&twa[0][0][0])[min(tid, 47)] = nt;
-        else (&amt[0][0][0])[min(tid, 191)] = nt;
+        (&amt[0][0][0])[min(tid, 191)] = nt;
     }
     __syncthreads();
     // the taps minus their window mean (r06): a tap constant over the FFT window
     // maps to the diagonal of Q' H G, so the chain now forms (D - diag h) u
     // itself and the one-tap input is y / h - acc / h (no + u per row and
-    // iteration); the mean over the unit's four quarters by the all-ones MFMA
-    // (NM: quarters on the K rows) or two DPP exchanges (quad layout)
+    // iteration); the mean over the unit's four quarters (the K rows) by the
+    // all-ones MFMA
 #pragma unroll
     for (int q = 0; q < NT; ++q) {
         double2 sq = taps[0][q];
 #pragma unroll
         for (int m = 1; m < 6; ++m) sq = c_add(sq, taps[m][q]);
-        if (NM) {
-            sq = make_double2(__builtin_amdgcn_mfma_f64_4x4x4f64(1.0, sq.x, 0.0, 0, 0, 0),
-                              __builtin_amdgcn_mfma_f64_4x4x4f64(1.0, sq.y, 0.0, 0, 0, 0));
-        } else {
-            sq = c_add(sq, dpp_c<QP_XOR1>(sq));
-            sq = c_add(sq, dpp_c<QP_XOR2>(sq));
-        }
+        sq = make_double2(__builtin_amdgcn_mfma_f64_4x4x4f64(1.0, sq.x, 0.0, 0, 0, 0),
+                          __builtin_amdgcn_mfma_f64_4x4x4f64(1.0, sq.y, 0.0, 0, 0, 0));
         const double2 mq = make_double2(sq.x * (1.0 / 24.0), sq.y * (1.0 / 24.0));
 #pragma unroll
         for (int m = 0; m < 6; ++m) taps[m][q] = c_sub(taps[m][q], mq);
@@ -1944,7 +1918,6 @@ __device__ __forceinline__ void pic_fft_body(const SchemeK& sk, const BandOrder&
         dmask |= dc >= 0 ? 1u << a : 0u;
         emask |= dc >= 0 && (dc & 1) ? 1u << a : 0u;
     }
-    const double sg1 = (r >> 1) ? -1.0 : 1.0, sg2 = (r & 1) ? -1.0 : 1.0;
     int ncnt = 0;
     // error-count weight of row a: data rows count 1, no-edge rows also 1 << 16
     auto cweight = [&](int a) -> int {
@@ -1996,38 +1969,28 @@ __device__ __forceinline__ void pic_fft_body(const SchemeK& sk, const BandOrder&
         ncnt = 0;
     }
     for (int it = 1; it <= niter; ++it) {
-        // an opaque zero keeps the per-iteration LDS twiddle reads inside the loop
+        // an opaque zero keeps the per-iteration LDS matrix reads inside the loop
         // (hoisted, they would hold 56 more registers)
         int oz = 0;
         asm volatile("" : "+v"(oz));
-        const int ro = r + oz;
-        // t = IDFT24(u): DFT-6 per lane, twiddle w24^(r m'), 4-point network
-        // across the quad (xor 2, lane twiddle, xor 1): lane r ends with the time
-        // samples 6 cq + m'
+        // t = IDFT24(u): DFT-6 per lane, then the 4-point network with the lane
+        // twiddle w24^(k m') (A_m, inverse): lane r ends with the time samples
+        // 6 r + m'
         double2 x[6];
 #pragma unroll
         for (int a = 0; a < 6; ++a) x[a] = u[a];
         dft6<1>(x);
         double2 t[6];
-        const int ai = (l & 3) + 4 * (l >> 4) + oz;             // NM: this lane's A entry
+        const int ai = (l & 3) + 4 * (l >> 4) + oz;             // this lane's A entry
 #pragma unroll
         for (int m = 0; m < 6; ++m) {
-            if (NM) {
-                const double2 am = amt[0][m][ai], b = x[p6(m)];
-                t[m] = mfma4_cmul(am, b);
-            } else {
-                const double2 p = c_mulf(x[p6(m)], twa[0][ro][m]);
-                const double2 pv = dpp_c<QP_XOR2>(p);
-                double2 e = make_double2(fma(sg1, p.x, pv.x), fma(sg1, p.y, pv.y));
-                e = quad_tw<1>(e, r == 3);
-                const double2 qv = dpp_c<QP_XOR1>(e);
-                t[m] = make_double2(fma(sg2, e.x, qv.x), fma(sg2, e.y, qv.y));
-            }
+            const double2 am = amt[0][m][ai], b = x[p6(m)];
+            t[m] = mfma4_cmul(am, b);
         }
         // channel, in place, last sample first: x[m] = sum_q IR_q[m] t[m - d_q];
         // t[-1] of the quarter is sample 5 of the previous quarter's lane (the
         // cyclic prefix for quarter 0)
-        const double2 tprev = NM ? bperm_c(((l + 48) & 63) * 4, t[5]) : dpp_c<QP_PREV>(t[5]);
+        const double2 tprev = bperm_c(((l + 48) & 63) * 4, t[5]);
 #pragma unroll
         for (int m = 5; m >= 0; --m) {
             const double2 tp = m ? t[m - 1] : tprev;
@@ -2036,20 +1999,10 @@ __device__ __forceinline__ void pic_fft_body(const SchemeK& sk, const BandOrder&
             for (int q = 0; q < NT; ++q) c_fma(acc, taps[m][q], ((SH >> q) & 1) ? tp : t[m]);
             t[m] = acc;
         }
-        // acc = qs gs DFT24(x): network across the quad (xor 1, lane twiddle,
-        // xor 2) back to lane r = output residue, twiddle qs gs w24^-(r m'), DFT-6
+        // acc = qs gs DFT24(x): the network back to lane r = output residue with
+        // the twiddle qs gs w24^-(i m') (A_m, forward), DFT-6
 #pragma unroll
-        for (int m = 0; m < 6; ++m) {
-            if (NM) {
-                x[m] = mfma4_cmul(amt[NM ? 1 : 0][m][ai], t[m]);
-            } else {
-                const double2 pv = dpp_c<QP_XOR1>(t[m]);
-                double2 f = make_double2(fma(sg2, t[m].x, pv.x), fma(sg2, t[m].y, pv.y));
-                f = quad_tw<-1>(f, r == 3);
-                const double2 qv = dpp_c<QP_XOR2>(f);
-                x[m] = c_mulf(make_double2(fma(sg1, f.x, qv.x), fma(sg1, f.y, qv.y)), twa[1][ro][m]);
-            }
-        }
+        for (int m = 0; m < 6; ++m) x[m] = mfma4_cmul(amt[1][m][ai], t[m]);
         dft6<-1>(x);
         // Yo and hcs at the first epilogue (not before the loop): the first chain
         // runs while y and h are still in flight (S0: formed above)
@@ -2106,10 +2059,10 @@ __device__ __forceinline__ void pic_fft_body(const SchemeK& sk, const BandOrder&
     }
 }
 
-template <int NT, int SH, bool TRACE, bool S0 = false, bool NM = false>
+template <int NT, int SH, bool TRACE, bool S0 = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_pic_fft(SchemeK sk, BandOrder ord, const double2* __restrict__ ir, int N, StorePerfectDetect o, int niter) {
-    pic_fft_body<NT, SH, TRACE, S0, NM>(sk, ord, ir, N, o, niter, blockIdx.x, gridDim.x);
+    pic_fft_body<NT, SH, TRACE, S0>(sk, ord, ir, N, o, niter, blockIdx.x, gridDim.x);
 }
 
 // ---------------------------------------------------------------------------
@@ -2154,10 +2107,10 @@ k_pic_fft(SchemeK sk, BandOrder ord, const double2* __restrict__ ir, int N, Stor
 // are read once per symbol instead of once per stage, decisions never leave
 // the registers, Bv / Bs of both variants are staged once.
 // The tap GEMM's A rows interleave the time quarters: tile t row c + 4k is tap
-// index 4t + k (q = idx / 6, window sample 6c + idx % 6) of quarter c, so the
-// lane quad of a unit pulls its quarter's 4 taps of the tile from one lane with
-// ds_bpermute (mic_taps): no LDS slab (k_mic_fft: 52 KB per block; r03's first
-// version: a 17 KB per-wave slab with a fence pair per tile).
+// index 4t + k (q = idx / 6, window sample 6c + idx % 6) of quarter c, so with
+// a unit's quarters on the 16-lane rows the GEMM's D registers already are the
+// lane's own taps (mic_taps): no LDS slab (k_mic_fft: 52 KB per block; r03's
+// first version: a 17 KB per-wave slab with a fence pair per tile).
 // ---------------------------------------------------------------------------
 struct Mic2Args {
     const double2* __restrict__ bv;   // [var][snr][NT][N][NP]
@@ -2177,22 +2130,17 @@ struct Mic2Args {
 
 __device__ __forceinline__ int mic_var(int s, int niter) { return (s == 0 || 2 * s <= niter) ? 0 : 1; }
 
-// Estimated taps of the lane's six window samples (quad layout: lane r of a unit
-// holds samples 6 cq + m) for the 16 units of a wave: MFMA GEMM (3M) with
+// Estimated taps of the lane's six window samples (lane = 16 cq + unit holds
+// samples 6 cq + m) for the 16 units of a wave: MFMA GEMM (3M) with
 // A(q, j, p) = Bv[q][klo + j][p] and B = hP (lane (g, jc): pilots 4 ks + g of
 // unit jc).  Tile t's A row i is tap index 4 t + (i >> 2) of time quarter i & 3,
 // so D register k of lane (g, jc) holds tap index 4 t + k of quarter g, unit jc:
-// the lane (unit ul, quarter cq) pulls its four taps of the tile from lane
-// 16 cq + ul with one ds_bpermute per dword, the same register in every lane
-// (r02-r03's per-wave LDS slab needed 17 KB per block and a fence pair per tile).
-// NM (quarters on the 16-lane rows, lane = 16 cq + unit): D register k of a
-// lane already is its tap index 4 t + k, no exchange at all.
-template <int NT, int NP, bool NM, class ALoad>
-__device__ __forceinline__ void mic_taps(double2 (&taps)[6][NT], const ALoad& A, const double2 (&hb)[NP / 4], int l,
-                                         int cq) {
+// the lane's own taps, no exchange at all (r02-r03's per-wave LDS slab needed
+// 17 KB per block and a fence pair per tile).
+template <int NT, int NP, class ALoad>
+__device__ __forceinline__ void mic_taps(double2 (&taps)[6][NT], const ALoad& A, const double2 (&hb)[NP / 4], int l) {
     constexpr int NIDX = 6 * NT, NTILE = (NIDX + 3) / 4, NKS = NP / 4;
-    const int g = l >> 4, jc = l & 15, ca = jc & 3, ka = jc >> 2, ul = l >> 2;
-    const int src = (16 * cq + ul) * 4;
+    const int g = l >> 4, jc = l & 15, ca = jc & 3, ka = jc >> 2;
     double br[NKS], bi[NKS], bsm[NKS];
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) {
@@ -2217,37 +2165,23 @@ __device__ __forceinline__ void mic_taps(double2 (&taps)[6][NT], const ALoad& A,
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int id2 = 4 * t + k;                     // compile-time
-            if (id2 < NIDX) {
-                const double2 tv = make_double2(p1[k] - p2[k], p3[k] - p1[k] - p2[k]);
-                taps[id2 % 6][id2 / 6] = NM ? tv : bperm_c(src, tv);
-            }
+            if (id2 < NIDX) taps[id2 % 6][id2 / 6] = make_double2(p1[k] - p2[k], p3[k] - p1[k] - p2[k]);
         }
     }
 }
 
-// x <- qs gs DFT24(sum_q taps_q .* IDFT24(x)(. - d_q)) of one symbol (k_pic_fft's
-// chain; twa: the lane twiddles staged in LDS, output scale folded in twa[1])
-// NM: k_pic_fft's matrix-core network (amt: A_m per [dir][m][i + 4 k], ai this
-// lane's entry; the previous quarter's sample by ds_bpermute)
-template <int NT, int SH, bool NM>
-__device__ __forceinline__ void mic_chain(double2 (&xx)[6], const double2 (&tp)[6][NT], const double2 (*twa)[4][6],
-                                          const double2 (*amt)[6][16], int ai, int l, int r, double sg1, double sg2) {
+// x <- qs gs DFT24(sum_q taps_q .* IDFT24(x)(. - d_q)) of one symbol: k_pic_fft's
+// chain with its matrix-core network (amt: A_m per [dir][m][i + 4 k], the output
+// scale folded into amt[1]; ai this lane's entry; the previous quarter's sample
+// by ds_bpermute)
+template <int NT, int SH>
+__device__ __forceinline__ void mic_chain(double2 (&xx)[6], const double2 (&tp)[6][NT], const double2 (*amt)[6][16],
+                                          int ai, int l) {
     dft6<1>(xx);
     double2 t[6];
 #pragma unroll
-    for (int m = 0; m < 6; ++m) {
-        if (NM) {
-            t[m] = mfma4_cmul(amt[0][m][ai], xx[p6(m)]);
-        } else {
-            const double2 p = c_mulf(xx[p6(m)], twa[0][r][m]);
-            const double2 pv = dpp_c<QP_XOR2>(p);
-            double2 e = make_double2(fma(sg1, p.x, pv.x), fma(sg1, p.y, pv.y));
-            e = quad_tw<1>(e, r == 3);
-            const double2 qv = dpp_c<QP_XOR1>(e);
-            t[m] = make_double2(fma(sg2, e.x, qv.x), fma(sg2, e.y, qv.y));
-        }
-    }
-    const double2 tprev = NM ? bperm_c(((l + 48) & 63) * 4, t[5]) : dpp_c<QP_PREV>(t[5]);
+    for (int m = 0; m < 6; ++m) t[m] = mfma4_cmul(amt[0][m][ai], xx[p6(m)]);
+    const double2 tprev = bperm_c(((l + 48) & 63) * 4, t[5]);
 #pragma unroll
     for (int m = 5; m >= 0; --m) {
         const double2 tq = m ? t[m - 1] : tprev;
@@ -2257,27 +2191,16 @@ __device__ __forceinline__ void mic_chain(double2 (&xx)[6], const double2 (&tp)[
         t[m] = acc;
     }
 #pragma unroll
-    for (int m = 0; m < 6; ++m) {
-        if (NM) {
-            xx[m] = mfma4_cmul(amt[1][m][ai], t[m]);
-        } else {
-            const double2 pv = dpp_c<QP_XOR1>(t[m]);
-            double2 f = make_double2(fma(sg2, t[m].x, pv.x), fma(sg2, t[m].y, pv.y));
-            f = quad_tw<-1>(f, r == 3);
-            const double2 qv = dpp_c<QP_XOR2>(f);
-            xx[m] = c_mulf(make_double2(fma(sg1, f.x, qv.x), fma(sg1, f.y, qv.y)), twa[1][r][m]);
-        }
-    }
+    for (int m = 0; m < 6; ++m) xx[m] = mfma4_cmul(amt[1][m][ai], t[m]);
     dft6<-1>(xx);
 }
 
 // Shared LDS tables of the two kernels: constellation, slicer grid, row tables of
-// the wave's symbol, lane twiddles, the per-row diag(D_hat) weight of a delayed tap.
+// the wave's symbol, the network's matrices, the per-row diag(D_hat) weight of a delayed tap.
 struct Mic2Tables {
     double2 sym[256];
     alignas(16) unsigned char sgrid[256];   // slice6's byte grid [iI][iQ], row stride 16
-    double2 twa[2][4][6];
-    double2 amt[2][6][16];            // NM network: A_m[i][k] at [dir][m][i + 4 k] (k_pic_fft's)
+    double2 amt[2][6][16];            // the 4-point network: A_m[i][k] at [dir][m][i + 4 k] (k_pic_fft's)
 };
 
 // One-tap + detection of the lane's six rows with diag(D_hat) = hd[a]; returns
@@ -2355,19 +2278,17 @@ struct Mic2Unit {
 // T_k the J0 kernel summed over pilot symbol k's window (twl: this symbol's
 // window, tsl: its sums), instead of the tap GEMM Bv hP (NT x 24 x NP complex
 // MACs per symbol and unit); diag(D_hat_s) from S_q = sum_k tsl[k] Z_s[q k].
-template <int NT, int SH, int NP, bool TRACE, bool PIL, bool NM, bool LR, class ALoad, class BsLoad>
+template <int NT, int SH, int NP, bool TRACE, bool PIL, bool LR, class ALoad, class BsLoad>
 __device__ __forceinline__ void mic2_stages(const SchemeK& sk, const Mic2Args& ma, const StorePerfectDetect& o,
                                             const Mic2Unit& mu,
                                             const Mic2Tables& tb, const double2* rpv, const int* rdc, const int* rpc,
                                             const double2* wrow, double2 (*shp)[NP][17],
                                             const double2 (*xpb)[17], int (*cntl), const ALoad& A, const BsLoad& Bs,
-                                            int row0, int unit, int unit_mf, int ul, int l, int r, int U, int R, int rl,
+                                            int row0, int unit, int ul, int l, int r, int U, int R, int rl,
                                             int snr, const double* twl = nullptr, const double* tsl = nullptr,
                                             double2 (*szz)[NT * MIC_NB][17] = nullptr, int unit0 = 0,
                                             const double2* bzl = nullptr, double2 (*vcst)[256] = nullptr) {
     constexpr int NZ = NT * MIC_NB;
-    const int cq = NM ? r : (r >> 1) + 2 * (r & 1);
-    const double sg1 = (r >> 1) ? -1.0 : 1.0, sg2 = (r & 1) ? -1.0 : 1.0;
     const double2 scale = make_double2(o.pf_scale_re, o.pf_scale_im);
     const bool valid = rl < o.rvalid;
     // per-unit operands (mu, loaded by the kernel); PIL: the LS factors isqk / x_p
@@ -2409,17 +2330,17 @@ __device__ __forceinline__ void mic2_stages(const SchemeK& sk, const Mic2Args& m
     // per lane, for diag(D_hat_s)); the data kernel prefetches both for stage
     // s + 1 at the end of stage s and folds hn4 into the window sums sn at once
     double2 hb[LR ? 1 : NP / 4], hn4[LR ? 1 : NP / 4];
-    // LR: Z of this stage (diag, then the next stage's taps), whole unit per lane
-    // (the data kernel; the pilot kernel reads them from its LDS szz instead)
-    // MLR (r06, the row layout NM): the low-rank taps and window sums on the
-    // matrix cores.  MIC_NB = 4 pilot symbols = the K rows of v_mfma_f64_4x4x4f64:
+    // LR (r06): the low-rank taps and window sums on the matrix cores, from Z of
+    // this stage (diag, then the next stage's taps; zc in the data kernel, the
+    // pilot kernel reads its LDS szz instead).
+    // MIC_NB = 4 pilot symbols = the K rows of v_mfma_f64_4x4x4f64:
     // the lane of quarter k (row k = l >> 4, unit l & 15 = 4 c + n) holds its
     // unit's Z[q][k] (B[k][n]) and T_k[6 i + a] with i = l & 3 (A[i][k], the same
     // for every block c), so D[i][n] = sum_k T_k[6 i + a] Z_n[q][k] is the tap of
     // sample 6 i + a in the unit's quarter-i lane: 2 MFMAs per (sample, tap)
     // instead of 8 FMAs, and a lane reads 2 of the NZ = 8 Z values per stage
-    constexpr bool MLR = LR && NM && MIC_NB == 4;
-    constexpr int NZR = LR && !PIL ? (MLR ? NT : NZ) : 1;
+    static_assert(MIC_NB == 4, "the low-rank products put the pilot symbols on the MFMA's four K rows");
+    constexpr int NZR = LR && !PIL ? NT : 1;
     double2 zc[NZR];
     // LR data kernel: the next stage's estimated taps, formed at the end of a stage
     // from its Z (r05: carrying the previous stage's Z instead cost 16 register
@@ -2427,75 +2348,32 @@ __device__ __forceinline__ void mic2_stages(const SchemeK& sk, const Mic2Args& m
     // stage's land in the same registers)
     constexpr int NTL = LR && !PIL ? 6 : 1;
     double2 ltp[NTL][NT];
-    // Z[q][l >> 4] of the lane's unit (MLR)
+    // Z[q][l >> 4] of the lane's unit
     auto zrow = [&](int sp, int q) -> double2 { return PIL ? szz[sp & 1][q * MIC_NB + (l >> 4)][ul] : zc[q % NZR]; };
     auto lr_taps = [&](double2 (&tp)[6][NT], int sp, int ozz) {
-        if constexpr (MLR) {
-            double2 zq[NT];
+        double2 zq[NT];
 #pragma unroll
-            for (int q = 0; q < NT; ++q) zq[q] = zrow(sp, q);
-#pragma unroll
-            for (int a = 0; a < 6; ++a) {
-                const double ta = twl[(l >> 4) * 24 + 6 * (l & 3) + a + ozz];
-#pragma unroll
-                for (int q = 0; q < NT; ++q)
-                    tp[a][q] = make_double2(__builtin_amdgcn_mfma_f64_4x4x4f64(ta, zq[q].x, 0.0, 0, 0, 0),
-                                            __builtin_amdgcn_mfma_f64_4x4x4f64(ta, zq[q].y, 0.0, 0, 0, 0));
-            }
-            return;
-        }
+        for (int q = 0; q < NT; ++q) zq[q] = zrow(sp, q);
 #pragma unroll
         for (int a = 0; a < 6; ++a) {
-            double tk[MIC_NB];
+            const double ta = twl[(l >> 4) * 24 + 6 * (l & 3) + a + ozz];
 #pragma unroll
-            for (int k = 0; k < MIC_NB; ++k) tk[k] = twl[k * 24 + 6 * cq + a + ozz];
-#pragma unroll
-            for (int q = 0; q < NT; ++q) {
-                double2 zk[MIC_NB];
-#pragma unroll
-                for (int k = 0; k < MIC_NB; ++k)
-                    zk[k] = PIL ? szz[sp & 1][q * MIC_NB + k][ul] : zc[(q * MIC_NB + k) % NZR];
-                double2 t = make_double2(tk[0] * zk[0].x, tk[0] * zk[0].y);
-#pragma unroll
-                for (int k = 1; k < MIC_NB; ++k) {
-                    t.x = fma(tk[k], zk[k].x, t.x);
-                    t.y = fma(tk[k], zk[k].y, t.y);
-                }
-                tp[a][q] = t;
-            }
+            for (int q = 0; q < NT; ++q)
+                tp[a][q] = make_double2(__builtin_amdgcn_mfma_f64_4x4x4f64(ta, zq[q].x, 0.0, 0, 0, 0),
+                                        __builtin_amdgcn_mfma_f64_4x4x4f64(ta, zq[q].y, 0.0, 0, 0, 0));
         }
     };
     // diag(D_hat_s) = qs gs sum_q w^(-l d_q) Bs_q(var_s) hP_s: window sums sn0 / sn1
     auto diag_sums = [&](int s, int ro, double2& sn0, double2& sn1) {
         sn0 = sn1 = make_double2(0.0, 0.0);
         bool f0 = true, f1 = true;                          // compile-time: first tap of each sum assigns
-        if constexpr (MLR) {
+        if constexpr (LR) {
             const double tsr = tsl[l >> 4];
 #pragma unroll
             for (int q = 0; q < NT; ++q) {
                 const double2 z = zrow(s, q);
                 const double2 sq = make_double2(__builtin_amdgcn_mfma_f64_4x4x4f64(tsr, z.x, 0.0, 0, 0, 0),
                                                 __builtin_amdgcn_mfma_f64_4x4x4f64(tsr, z.y, 0.0, 0, 0, 0));
-                if ((SH >> q) & 1) {
-                    sn1 = f1 ? sq : c_add(sn1, sq);
-                    f1 = false;
-                } else {
-                    sn0 = f0 ? sq : c_add(sn0, sq);
-                    f0 = false;
-                }
-            }
-        } else if constexpr (LR) {
-#pragma unroll
-            for (int q = 0; q < NT; ++q) {
-                double2 zk[MIC_NB];
-#pragma unroll
-                for (int k = 0; k < MIC_NB; ++k) zk[k] = PIL ? szz[s & 1][q * MIC_NB + k][ul] : zc[(q * MIC_NB + k) % NZR];
-                double2 sq = make_double2(tsl[0] * zk[0].x, tsl[0] * zk[0].y);
-#pragma unroll
-                for (int k = 1; k < MIC_NB; ++k) {
-                    sq.x = fma(tsl[k], zk[k].x, sq.x);
-                    sq.y = fma(tsl[k], zk[k].y, sq.y);
-                }
                 if ((SH >> q) & 1) {
                     sn1 = f1 ? sq : c_add(sn1, sq);
                     f1 = false;
@@ -2511,14 +2389,9 @@ __device__ __forceinline__ void mic2_stages(const SchemeK& sk, const Mic2Args& m
                 double2 sq = c_mul(Bs(vs, q, ro * (NP / 4)), hn4[0]);
 #pragma unroll
                 for (int k = 1; k < NP / 4; ++k) c_fma(sq, Bs(vs, q, ro * (NP / 4) + k), hn4[k]);
-                if (NM) {
-                    // sum over the unit's four quarters (rows): ones(4 x 4) x B
-                    sq = make_double2(__builtin_amdgcn_mfma_f64_4x4x4f64(1.0, sq.x, 0.0, 0, 0, 0),
-                                      __builtin_amdgcn_mfma_f64_4x4x4f64(1.0, sq.y, 0.0, 0, 0, 0));
-                } else {
-                    sq = c_add(sq, dpp_c<QP_XOR1>(sq));
-                    sq = c_add(sq, dpp_c<QP_XOR2>(sq));
-                }
+                // sum over the unit's four quarters (rows): ones(4 x 4) x B
+                sq = make_double2(__builtin_amdgcn_mfma_f64_4x4x4f64(1.0, sq.x, 0.0, 0, 0, 0),
+                                  __builtin_amdgcn_mfma_f64_4x4x4f64(1.0, sq.y, 0.0, 0, 0, 0));
                 if ((SH >> q) & 1) {
                     sn1 = f1 ? sq : c_add(sn1, sq);
                     f1 = false;
@@ -2532,19 +2405,16 @@ __device__ __forceinline__ void mic2_stages(const SchemeK& sk, const Mic2Args& m
     };
     for (int s = 0; s <= ma.niter; ++s) {
         // an opaque zero in the per-stage LDS indices: hoisted out of the stage
-        // loop, the operator / twiddle reads of both variants would stay live
+        // loop, the operator / matrix reads of both variants would stay live
         // across it (k_pic_fft's lesson)
         int oz = 0;
         asm volatile("" : "+v"(oz));
         const int ro = r + oz;
         double2 sn0, sn1;
-        if (MLR && !PIL) {
+        if (LR && !PIL) {
 #pragma unroll
             for (int q = 0; q < NZR; ++q)
                 zc[q] = buf_ld2(rza, (unsigned)(unit + (l >> 4) * U) * 16u, (unsigned)((s * NZ + q * MIC_NB) * U) * 16u);
-        } else if (LR && !PIL) {
-#pragma unroll
-            for (int j = 0; j < NZR; ++j) zc[j] = buf_ld2(rza, (unsigned)unit * 16u, (unsigned)((s * NZ + j) * U) * 16u);
         } else if (!LR && !PIL) {
 #pragma unroll
             for (int k = 0; k < NP / 4; ++k) hn4[k] = ma.hpa[(size_t)s * NP * U + (size_t)(r * (NP / 4) + k) * U + unit];
@@ -2559,22 +2429,22 @@ __device__ __forceinline__ void mic2_stages(const SchemeK& sk, const Mic2Args& m
             if constexpr (LR && !PIL) {
                 // formed at the end of stage s - 1 (ltp)
             } else if constexpr (LR) {
-                // T_k of the lane's six samples (this symbol's window, quarter cq)
+                // T_k of the lane's six samples (this symbol's window, quarter l & 3)
                 lr_taps(taps, s - 1, oz);
             } else {
                 if (PIL)
 #pragma unroll
                     for (int ks = 0; ks < NP / 4; ++ks) hb[ks] = shp[(s - 1) & 1][4 * ks + (l >> 4)][l & 15];
-                mic_taps<NT, NP, NM>(taps, [&](int q, int j, int p) { return A(mic_var(s - 1, ma.niter), q, j + oz, p); },
-                                     hb, l, cq);
+                mic_taps<NT, NP>(taps, [&](int q, int j, int p) { return A(mic_var(s - 1, ma.niter), q, j + oz, p); },
+                                 hb, l);
             }
             double2 x[6];
 #pragma unroll
             for (int a = 0; a < 6; ++a) x[a] = v[a];
             if constexpr (LR && !PIL)
-                mic_chain<NT, SH, NM>(x, ltp, tb.twa, tb.amt, (l & 3) + 4 * (l >> 4) + oz, l, ro, sg1, sg2);
+                mic_chain<NT, SH>(x, ltp, tb.amt, (l & 3) + 4 * (l >> 4) + oz, l);
             else
-                mic_chain<NT, SH, NM>(x, taps, tb.twa, tb.amt, (l & 3) + 4 * (l >> 4) + oz, l, ro, sg1, sg2);
+                mic_chain<NT, SH>(x, taps, tb.amt, (l & 3) + 4 * (l >> 4) + oz, l);
             // y_ic = y - (D_hat_{s-1} - diag) v  (script:482-484); LR: the taps are
             // mean-free over the window (centred Tw, build_mic_lr), so the chain
             // already is (D_hat - diag) v (r06: 48 FP64 operations per stage fewer)
@@ -2680,7 +2550,7 @@ __device__ __forceinline__ void mic2_stages(const SchemeK& sk, const Mic2Args& m
             // stage s + 1's operands: hP_s (tap GEMM) and hP_{s+1} (diag)
             const double2* __restrict__ hs = ma.hpa + (size_t)s * NP * U;
 #pragma unroll
-            for (int ks = 0; ks < NP / 4; ++ks) hb[ks] = hs[(size_t)(4 * ks + (l >> 4)) * U + unit_mf];
+            for (int ks = 0; ks < NP / 4; ++ks) hb[ks] = hs[(size_t)(4 * ks + (l >> 4)) * U + unit];
         }
         if (ma.mse_err) {
             double me = 0.0, mp = 0.0;
@@ -2696,15 +2566,15 @@ __device__ __forceinline__ void mic2_stages(const SchemeK& sk, const Mic2Args& m
     }
 }
 
-// LDS tables of a block: constellation / slicer grid (256 entries), lane twiddles
-// Two-phase table staging for 256-thread blocks (r05): mic2_tab_load issues
+// LDS tables of a block: constellation / slicer grid (256 entries), the network's
+// matrices.  Two-phase table staging for 256-thread blocks (r05): mic2_tab_load issues
 // every global read of the block tables (one entry of each per thread, clamped,
 // unconditional) and of the symbol's row tables (thread rt = min(t, 23)), the
 // caller then issues its per-unit reads, and mic2_tab_store writes LDS waiting
 // only for the table reads (vmcnt retires in order).  A read under a branch
 // waited with vmcnt(0) for everything issued before it.
 struct Mic2TabLoad {
-    double2 a, tw, t0, pv, wr;
+    double2 a, t0, pv, wr;
     int rd, pc;
     unsigned g;
 };
@@ -2714,7 +2584,6 @@ struct Mic2TabLoad {
 __device__ __forceinline__ void mic2_tab_load(Mic2TabLoad& L, const SchemeK& sk, int blk, int tid, int t) {
     L.a = sk.ct_sym[tid];
     L.g = sk.ct_grid[min(tid, 63)];
-    L.tw = sk.ct_twa[min(tid, 47)];
     L.t0 = sk.ct_amt[min(tid, 191)];
     const int i = blk * 24 + min(t, 23);
     L.pv = sk.ct_rpv[i];
@@ -2726,7 +2595,6 @@ __device__ __forceinline__ void mic2_tab_store(const Mic2TabLoad& L, Mic2Tables&
                                                double2* wrow, int tid, int t) {
     tb.sym[tid] = L.a;
     ((unsigned*)tb.sgrid)[min(tid, 63)] = L.g;
-    (&tb.twa[0][0][0])[min(tid, 47)] = L.tw;
     (&tb.amt[0][0][0])[min(tid, 191)] = L.t0;
     // row tables (threads t >= 24 rewrite row 23's entries)
     const int rt = min(t, 23);
@@ -2744,13 +2612,6 @@ __device__ __forceinline__ void mic2_tables(Mic2Tables& tb, const StorePerfectDe
         const int g = o.grid_sym[min(gi * o.nQ + gq, o.nI * o.nQ - 1)];
         tb.sym[i] = stage_sym(make_double2(i < o.M ? a.x : 0.0, i < o.M ? a.y : 0.0), o.pv_uni, o.pv_re, o.pv_im);
         tb.sgrid[i] = (unsigned char)(gi < o.nI && gq < o.nQ ? g : 0);
-    }
-    if (tid < 48) {
-        const int e = ((tid / 6) % 4) * (tid % 6);
-        const double2 tw = kW24[e % 12];
-        const int dir = tid / 24;
-        const double2 v = e >= 12 ? make_double2(-tw.x, -tw.y) : tw;
-        tb.twa[dir][(tid / 6) % 4][tid % 6] = dir ? c_mul(scale, make_double2(v.x, -v.y)) : v;
     }
     for (int i = tid; i < 192; i += nth) {
         const int dir = i / 96, m = (i / 16) % 6, ii = i & 3, kk = (i >> 2) & 3;
@@ -2782,7 +2643,7 @@ __device__ __forceinline__ void mic2_rows(double2* rpv, int* rdc, int* rpc, doub
 
 // One wave per pilot symbol (blockDim = 64 npb, npb <= 4), 16 units per block
 // (vb / vn: the block index and grid size, as pic_fft_body's)
-template <int NT, int SH, int NP, bool TRACE, bool NM, bool LR>
+template <int NT, int SH, int NP, bool TRACE, bool LR>
 __device__ __forceinline__ void mic_pilot_body(const SchemeK& sk, const Mic2Args& ma, const StorePerfectDetect& o, int vb,
                                                int vn) {
     constexpr int NZ = NT * MIC_NB;
@@ -2799,7 +2660,7 @@ __device__ __forceinline__ void mic_pilot_body(const SchemeK& sk, const Mic2Args
     // SQ_LDS_BANK_CONFLICT of the pass -33 %)
     __shared__ double2 bzl[LR ? 2 * NZ * (NP + 1) : 1];
     __shared__ int cntl[4][PM_MAXIT + 1];
-    const int tid = threadIdx.x, l = tid & 63, r = NM ? l >> 4 : l & 3;
+    const int tid = threadIdx.x, l = tid & 63, r = l >> 4;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6), nw = blockDim.x >> 6;
     const int U = o.U, R = o.R;
     // 16-unit group, SNR-fastest inside each XCD's contiguous range (r05): the
@@ -2811,8 +2672,8 @@ __device__ __forceinline__ void mic_pilot_body(const SchemeK& sk, const Mic2Args
         const int L = xcd_remap(vb, vn), nch = o.U / o.R;
         ug16 = (L % nch) * (o.R / 16) + L / nch;
     }
-    const int ul = NM ? l & 15 : l >> 2;
-    const int unit = ug16 * 16 + ul, unit_mf = ug16 * 16 + (l & 15);
+    const int ul = l & 15;
+    const int unit = ug16 * 16 + ul;
     const int rl = unit % R;
     const int snr = o.snr0 + (ug16 * 16) / R;
     const int blk = ma.blks[w];
@@ -2855,9 +2716,9 @@ __device__ __forceinline__ void mic_pilot_body(const SchemeK& sk, const Mic2Args
     // reloaded at the W -> W0 switch: 40 more VGPRs, 1.97 -> 2.28 ms per step)
     auto A = [&](int var, int q, int j, int p) { return bvb[var * vstride + ((size_t)q * ma.N + j) * NP + p]; };
     auto Bs = [&](int var, int q, int p) { return bss[LR ? 0 : w][var][q][p]; };
-    mic2_stages<NT, SH, NP, TRACE, true, NM, LR>(sk, ma, o, mu, tb, rpv[w], rdc[w], rpc[w], wrow[w], shp, xpb, cntl[w], A,
-                                                 Bs, row0, unit, unit_mf, ul, l, r, U, R, rl, snr, twp[LR ? w : 0],
-                                                 twp[LR ? w : 0] + MIC_NB * 24, szz, ug16 * 16, bzl);
+    mic2_stages<NT, SH, NP, TRACE, true, LR>(sk, ma, o, mu, tb, rpv[w], rdc[w], rpc[w], wrow[w], shp, xpb, cntl[w], A, Bs,
+                                             row0, unit, ul, l, r, U, R, rl, snr, twp[LR ? w : 0],
+                                             twp[LR ? w : 0] + MIC_NB * 24, szz, ug16 * 16, bzl);
     __syncthreads();
     // one atomic per (stage, edge) per block
     for (int i = tid; i < 2 * (ma.niter + 1); i += blockDim.x) {
@@ -2869,13 +2730,13 @@ __device__ __forceinline__ void mic_pilot_body(const SchemeK& sk, const Mic2Args
     }
 }
 
-template <int NT, int SH, int NP, bool TRACE, bool NM = false, bool LR = false>
+template <int NT, int SH, int NP, bool TRACE, bool LR = false>
 __global__ void __launch_bounds__(256) k_mic_pilot(SchemeK sk, Mic2Args ma, StorePerfectDetect o) {
-    mic_pilot_body<NT, SH, NP, TRACE, NM, LR>(sk, ma, o, blockIdx.x, gridDim.x);
+    mic_pilot_body<NT, SH, NP, TRACE, LR>(sk, ma, o, blockIdx.x, gridDim.x);
 }
 
 // 64 units x one data symbol per block (4 waves x 16 units)
-template <int NT, int SH, int NP, bool TRACE, bool NM = false, bool LR = false>
+template <int NT, int SH, int NP, bool TRACE, bool LR = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_mic_data(SchemeK sk, BandOrder ord, Mic2Args ma, StorePerfectDetect o) {
     __shared__ Mic2Tables tb;
@@ -2890,12 +2751,12 @@ k_mic_data(SchemeK sk, BandOrder ord, Mic2Args ma, StorePerfectDetect o) {
     int ug, bi;
     band_block(ord, ma.nb, ug, bi);
     const int blk = ma.blks[bi];
-    const int tid = threadIdx.x, l = tid & 63, r = NM ? l >> 4 : l & 3;
+    const int tid = threadIdx.x, l = tid & 63, r = l >> 4;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int U = o.U, R = o.R;
     const int snr = o.snr0 + (ug * WAVE) / R;
-    const int ul = NM ? l & 15 : l >> 2;
-    const int unit = ug * WAVE + w * 16 + ul, unit_mf = ug * WAVE + w * 16 + (l & 15);
+    const int ul = l & 15;
+    const int unit = ug * WAVE + w * 16 + ul;
     const int rl = unit % R;
     const int row0 = sk.QH.row0[blk], klo = sk.QH.klo[blk];
     Mic2Unit mu;
@@ -2935,9 +2796,9 @@ k_mic_data(SchemeK sk, BandOrder ord, Mic2Args ma, StorePerfectDetect o) {
     __syncthreads();
     auto A = [&](int var, int q, int j, int p) { return sbv[LR ? 0 : var][q][LR ? 0 : j][p]; };
     auto Bs = [&](int var, int q, int p) { return bss[var][q][p]; };
-    mic2_stages<NT, SH, NP, TRACE, false, NM, LR>(sk, ma, o, mu, tb, rpv, rdc, rpc, wrow, nullptr, nullptr, cntl[w], A, Bs,
-                                                  row0, unit, unit_mf, ul, l, r, U, R, rl, snr, twd,
-                                                  twd + MIC_NB * 24, nullptr, 0, nullptr, vcst);
+    mic2_stages<NT, SH, NP, TRACE, false, LR>(sk, ma, o, mu, tb, rpv, rdc, rpc, wrow, nullptr, nullptr, cntl[w], A, Bs,
+                                              row0, unit, ul, l, r, U, R, rl, snr, twd, twd + MIC_NB * 24, nullptr, 0,
+                                              nullptr, vcst);
     __syncthreads();
     for (int i = tid; i < 2 * (ma.niter + 1); i += 256) {
         const int s = i >> 1, edge = i & 1;
@@ -2959,7 +2820,7 @@ k_mic_data(SchemeK sk, BandOrder ord, Mic2Args ma, StorePerfectDetect o) {
 // (S_q = the window sum of tap q).  Replaces the G band, k_channel_apply, the
 // diag(D) band and the noisy Q^H band: s and r0 never reach memory.  A
 // realisation's four time quarters sit on the four 16-lane rows (lane = 16 r +
-// realisation, k_pic_fft's NM layout), block = 64 realisations x one symbol; the
+// realisation, k_pic_fft's layout), block = 64 realisations x one symbol; the
 // 4-point network of both transforms is one complex 4 x 4 product per sample
 // on the matrix cores (r05: the DPP network cost 100 cycles per sample and
 // wave against 72, and the quad sums of diag(D) are one ones-MFMA each).
@@ -3258,11 +3119,10 @@ static Mic2Args mic2_args(const SchemeK& sk, const MmseK& mm, const ChannelK& ch
 }
 
 unsigned launch_mmse_stages(hipStream_t s, const SchemeK& sk, const MmseK& mm, const ChannelK& ch, McBuffers& b,
-                            const PerfectDetectArgs* pd, int niter, int xcd, int part, bool nm, bool lr) {
+                            const PerfectDetectArgs* pd, int niter, int xcd, int part, bool lr) {
     StorePerfectDetect o = chain_detect(sk, b, pd, 0);
     Mic2Args ma = mic2_args(sk, mm, ch, b, pd, niter);
-    // the low-rank operator: built (build_mic_lr), MIC_NB pilot symbols, Z buffer;
-    // the data pass on the matrix-core network (the caller requires mic_net bit 0)
+    // the low-rank operator: built (build_mic_lr), MIC_NB pilot symbols, Z buffer
     const bool use_lr = lr && mm.Bz && mm.Tw && mm.Ts && b.za && mm.npb == MIC_NB;
     const int sh = pic_fft_shift(ch);
     // pilot symbols: one wave each, 16 units per block
@@ -3270,16 +3130,11 @@ unsigned launch_mmse_stages(hipStream_t s, const SchemeK& sk, const MmseK& mm, c
     ma.nb = mm.npb;
     if (part & 1) {
         const dim3 grid(b.U / 16), blk(64 * mm.npb);
-        const bool pnm = nm;
 #define LAUNCH_MP(NTV, SHV)                                                                                  \
     do {                                                                                                     \
-        if (use_lr && b.tr && pnm) hipLaunchKernelGGL((k_mic_pilot<NTV, SHV, 16, true, true, true>), grid, blk, 0, s, sk, ma, o); \
-        else if (use_lr && pnm) hipLaunchKernelGGL((k_mic_pilot<NTV, SHV, 16, false, true, true>), grid, blk, 0, s, sk, ma, o); \
-        else if (use_lr && b.tr) hipLaunchKernelGGL((k_mic_pilot<NTV, SHV, 16, true, false, true>), grid, blk, 0, s, sk, ma, o); \
-        else if (use_lr) hipLaunchKernelGGL((k_mic_pilot<NTV, SHV, 16, false, false, true>), grid, blk, 0, s, sk, ma, o); \
-        else if (b.tr && pnm) hipLaunchKernelGGL((k_mic_pilot<NTV, SHV, 16, true, true>), grid, blk, 0, s, sk, ma, o); \
+        if (use_lr && b.tr) hipLaunchKernelGGL((k_mic_pilot<NTV, SHV, 16, true, true>), grid, blk, 0, s, sk, ma, o); \
+        else if (use_lr) hipLaunchKernelGGL((k_mic_pilot<NTV, SHV, 16, false, true>), grid, blk, 0, s, sk, ma, o); \
         else if (b.tr) hipLaunchKernelGGL((k_mic_pilot<NTV, SHV, 16, true>), grid, blk, 0, s, sk, ma, o);   \
-        else if (pnm) hipLaunchKernelGGL((k_mic_pilot<NTV, SHV, 16, false, true>), grid, blk, 0, s, sk, ma, o); \
         else hipLaunchKernelGGL((k_mic_pilot<NTV, SHV, 16, false>), grid, blk, 0, s, sk, ma, o);            \
     } while (0)
         if (ch.ntap == 1) LAUNCH_MP(1, 0);
@@ -3292,19 +3147,13 @@ unsigned launch_mmse_stages(hipStream_t s, const SchemeK& sk, const MmseK& mm, c
     if (part & 2) {
         const BandOrder om{b.U / WAVE, b.U / b.R, b.R / WAVE, xcd};
         const dim3 grid((b.U / WAVE) * mm.ndb), blk(256);
-        const bool dlr = use_lr && nm;
 #define LAUNCH_MD(NTV, SHV)                                                                                  \
     do {                                                                                                     \
-        if (dlr && b.tr) hipLaunchKernelGGL((k_mic_data<NTV, SHV, 16, true, true, true>), grid, blk, 0, s, sk, om, ma, o); \
-        else if (dlr) hipLaunchKernelGGL((k_mic_data<NTV, SHV, 16, false, true, true>), grid, blk, 0, s, sk, om, ma, o); \
-        else if (b.tr && nm) hipLaunchKernelGGL((k_mic_data<NTV, SHV, 16, true, true>), grid, blk, 0, s, sk, om, ma, o); \
+        if (use_lr && b.tr) hipLaunchKernelGGL((k_mic_data<NTV, SHV, 16, true, true>), grid, blk, 0, s, sk, om, ma, o); \
+        else if (use_lr) hipLaunchKernelGGL((k_mic_data<NTV, SHV, 16, false, true>), grid, blk, 0, s, sk, om, ma, o); \
         else if (b.tr) hipLaunchKernelGGL((k_mic_data<NTV, SHV, 16, true>), grid, blk, 0, s, sk, om, ma, o); \
-        else if (nm) hipLaunchKernelGGL((k_mic_data<NTV, SHV, 16, false, true>), grid, blk, 0, s, sk, om, ma, o); \
         else hipLaunchKernelGGL((k_mic_data<NTV, SHV, 16, false>), grid, blk, 0, s, sk, om, ma, o);         \
     } while (0)
-        if (use_lr && !dlr)
-            throw std::logic_error("launch_mmse_stages: the low-rank pilot pass needs the low-rank data pass "
-                                   "(mic_net bit 0)");
         if (ch.ntap == 1) LAUNCH_MD(1, 0);
         else if (sh == 1) LAUNCH_MD(2, 1);
         else LAUNCH_MD(2, 2);
@@ -3324,20 +3173,17 @@ unsigned launch_perfect_chain(hipStream_t s, const Opts& op, const SchemeK& sk, 
     // k_mic_data); otherwise stage 0 came from the stage kernel (u in HBM)
     if (!(o.scI != 0.0))
         throw std::logic_error("launch_perfect_chain: the chain's slicer scale is zero");
-#define LAUNCH_PF(NTV, SHV, S0V, NMV)                                                                               \
-    do {                                                                                                             \
-        if (b.tr)                                                                                                    \
-            hipLaunchKernelGGL((k_pic_fft<NTV, SHV, true, S0V, NMV>), grid, blk, 0, s, sk, om, b.ir, ch.N, o, niter);  \
-        else                                                                                                         \
-            hipLaunchKernelGGL((k_pic_fft<NTV, SHV, false, S0V, NMV>), grid, blk, 0, s, sk, om, b.ir, ch.N, o, niter); \
+#define LAUNCH_PF(NTV, SHV, S0V)                                                                               \
+    do {                                                                                                        \
+        if (b.tr)                                                                                               \
+            hipLaunchKernelGGL((k_pic_fft<NTV, SHV, true, S0V>), grid, blk, 0, s, sk, om, b.ir, ch.N, o, niter);  \
+        else                                                                                                    \
+            hipLaunchKernelGGL((k_pic_fft<NTV, SHV, false, S0V>), grid, blk, 0, s, sk, om, b.ir, ch.N, o, niter); \
     } while (0)
-    // Opts::pic_net: the 4-point network on the matrix cores (1) or by DPP (0)
-#define LAUNCH_PF2(NTV, SHV)                              \
-    do {                                                  \
-        if (stage0 && op.pic_net) LAUNCH_PF(NTV, SHV, true, true);    \
-        else if (stage0) LAUNCH_PF(NTV, SHV, true, false);            \
-        else if (op.pic_net) LAUNCH_PF(NTV, SHV, false, true);        \
-        else LAUNCH_PF(NTV, SHV, false, false);                       \
+#define LAUNCH_PF2(NTV, SHV)                        \
+    do {                                            \
+        if (stage0) LAUNCH_PF(NTV, SHV, true);      \
+        else LAUNCH_PF(NTV, SHV, false);            \
     } while (0)
     const int sh = pic_fft_shift(ch);
     if (ch.ntap == 1) LAUNCH_PF2(1, 0);
@@ -4003,7 +3849,7 @@ __global__ void __launch_bounds__(256)
 }
 
 // The unfused W contraction of 32-row blocks (FBMC, C5) as ONE GEMM per row
-// tile (k_wrow3, Opts::wrow): y_est[r] = y[r] - sum_(c,p) W[(r,c),p] X[(c,p)]
+// tile (k_wrow3): y_est[r] = y[r] - sum_(c,p) W[(r,c),p] X[(c,p)]
 // with X[(c,p)] = hP_p v_c per unit.  M = the block's rows (two 16-row tiles),
 // K = (column, pilot), N = units: the pair tile t = 2 c + h of k_wpair3's
 // storage IS the A fragment of row tile h and column c (pairs q = 32 c + r), so
@@ -4197,7 +4043,7 @@ unsigned launch_wcontract(hipStream_t s, const Opts& op, const SchemeK& sk, cons
     // packed band where no pair tiles exist (a block wider than 32 rows) or on
     // request (Opts::wcontract_valu)
     const bool pair_ok = mm.Wp3 && (b.U % 64) == 0 && (b.R % 64) == 0 && !op.wcontract_valu;
-    if (pair_ok && op.wrow && mm.Pb.rbp == 32) {
+    if (pair_ok && mm.Pb.rbp == 32) {
         // 32-row blocks: one GEMM per row tile, no per-tile epilogue (k_wrow3)
         const dim3 grid(b.U / 64, mm.Pb.nblk);
 #define LAUNCH_WR(NKSV)                                                                                            \
@@ -4210,19 +4056,14 @@ unsigned launch_wcontract(hipStream_t s, const Opts& op, const SchemeK& sk, cons
         return PATH_WROW3;
     }
     if (pair_ok) {
+        // 24-row blocks (PairBand::rbp is 24 or 32)
         const dim3 grid(b.U / 64, mm.Pb.nblk);
-#define LAUNCH_W3(RBPV, NKSV)                                                                                  \
-    hipLaunchKernelGGL((k_wpair3<RBPV, NKSV, false>), grid, dim3(256), 0, s, mm.Pb, mm.Wp3, mm.wp_elems, var,    \
+#define LAUNCH_W3(NKSV)                                                                                        \
+    hipLaunchKernelGGL((k_wpair3<24, NKSV, false>), grid, dim3(256), 0, s, mm.Pb, mm.Wp3, mm.wp_elems, var,      \
                        mm.nsnr, b.snr0, b.R, b.U, b.hp, b.v, b.y, b.yest, sk, FuseArgs{})
-        if (mm.Pb.rbp == 24) {
-            if (mm.Pb.nks == 2) LAUNCH_W3(24, 2);
-            else if (mm.Pb.nks == 4) LAUNCH_W3(24, 4);
-            else LAUNCH_W3(24, 8);
-        } else {
-            if (mm.Pb.nks == 2) LAUNCH_W3(32, 2);
-            else if (mm.Pb.nks == 4) LAUNCH_W3(32, 4);
-            else LAUNCH_W3(32, 8);
-        }
+        if (mm.Pb.nks == 2) LAUNCH_W3(2);
+        else if (mm.Pb.nks == 4) LAUNCH_W3(4);
+        else LAUNCH_W3(8);
 #undef LAUNCH_W3
         return PATH_WPAIR3;
     }
@@ -4437,7 +4278,8 @@ __global__ void __launch_bounds__(64) k_ls(SchemeK sk, StageArgs st, const doubl
 // decisions for k_precode.  diag(D_hat) is written only for traces; the
 // contraction uses a W band with a zero diagonal, so nothing else reads it.
 // Flat grid, row block fastest (the blocks of one unit group share hP in L2).
-template <int NPT, int RB, bool PERF, bool MSE>
+static constexpr int STAGE_RB = 8;                         // rows per wave of k_stage_fused
+template <int NPT, bool PERF, bool MSE>
 __global__ void __launch_bounds__(256) k_stage_fused(SchemeK sk, StageArgs st, int nrb, const double2* __restrict__ Wd,
                                                      const double2* __restrict__ xp,
                                                      const uint16_t* __restrict__ sidx,
@@ -4446,6 +4288,7 @@ __global__ void __launch_bounds__(256) k_stage_fused(SchemeK sk, StageArgs st, i
                                                      uint16_t* __restrict__ qe, uint16_t* __restrict__ qp,
                                                      double2* __restrict__ v, double2* __restrict__ u,
                                                      unsigned long long* __restrict__ counters) {
+    constexpr int RB = STAGE_RB;
     __shared__ double2 sym[256];
     __shared__ SlicerLds slt;
     __shared__ double2 shp[NPT * 64];                      // the block's 64 units' LS pilot estimates
@@ -4610,32 +4453,15 @@ __global__ void __launch_bounds__(256) k_stage_fused(SchemeK sk, StageArgs st, i
 
 template <int NPT>
 static void launch_stage_fused_np(hipStream_t s, const SchemeK& sk, const StageArgs& st, const MmseK& mm, McBuffers& b,
-                                  unsigned long long* counters, int rb) {
-    const int ug = b.U / 64;
-    uint16_t* qe_ = b.qe;
-    uint16_t* qp_ = b.qp;
-#define LAUNCH_SF(RBV)                                                                                          \
-    {                                                                                                           \
-        const int nrb = (sk.LK + 4 * (RBV) - 1) / (4 * (RBV));                                                  \
-        if (st.mse_err) {                                                                                       \
-            if (st.perfect)                                                                                     \
-                hipLaunchKernelGGL((k_stage_fused<NPT, RBV, true, true>), dim3(ug * nrb), dim3(256), 0, s, sk, st, \
-                                   nrb, mm.Wd, b.xp, b.sidx, b.h, b.hp, b.hest, qe_, qp_, b.v, b.u, counters); \
-            else                                                                                                \
-                hipLaunchKernelGGL((k_stage_fused<NPT, RBV, false, true>), dim3(ug * nrb), dim3(256), 0, s, sk,  \
-                                   st, nrb, mm.Wd, b.xp, b.sidx, b.h, b.hp, b.hest, qe_, qp_, b.v, b.u,       \
-                                   counters);                                                                   \
-        } else if (st.perfect)                                                                                  \
-            hipLaunchKernelGGL((k_stage_fused<NPT, RBV, true, false>), dim3(ug * nrb), dim3(256), 0, s, sk, st,   \
-                               nrb, mm.Wd, b.xp, b.sidx, b.h, b.hp, b.hest, qe_, qp_, b.v, b.u, counters);     \
-        else                                                                                                    \
-            hipLaunchKernelGGL((k_stage_fused<NPT, RBV, false, false>), dim3(ug * nrb), dim3(256), 0, s, sk, st,  \
-                               nrb, mm.Wd, b.xp, b.sidx, b.h, b.hp, b.hest, qe_, qp_, b.v, b.u, counters);     \
-        return;                                                                                                 \
-    }
-    if (rb == 4) LAUNCH_SF(4)
-    if (rb == 16) LAUNCH_SF(16)
-    LAUNCH_SF(8)
+                                  unsigned long long* counters) {
+    const int ug = b.U / 64, nrb = (sk.LK + 4 * STAGE_RB - 1) / (4 * STAGE_RB);
+#define LAUNCH_SF(PERFV, MSEV)                                                                                \
+    hipLaunchKernelGGL((k_stage_fused<NPT, PERFV, MSEV>), dim3(ug * nrb), dim3(256), 0, s, sk, st, nrb, mm.Wd, b.xp, \
+                       b.sidx, b.h, b.hp, b.hest, b.qe, b.qp, b.v, b.u, counters)
+    if (st.mse_err && st.perfect) LAUNCH_SF(true, true);
+    else if (st.mse_err) LAUNCH_SF(false, true);
+    else if (st.perfect) LAUNCH_SF(true, false);
+    else LAUNCH_SF(false, false);
 #undef LAUNCH_SF
 }
 
@@ -4669,12 +4495,12 @@ unsigned launch_stage(hipStream_t s, const Opts& op, const SchemeK& sk, const Mm
     st.mse_pow = b.mse_pow;
     const int rblk = (sk.LK + DSCE_RB - 1) / DSCE_RB;
     // select-mode schemes: k_ls + one fused pass (Opts::stage_split keeps the
-    // 3-kernel path; Opts::stage_rb = rows per wave of the fused pass, 4 | 8 | 16)
+    // 3-kernel path)
     if (stage_fused_ok(op, sk)) {
         hipLaunchKernelGGL(k_ls, dim3(b.U / WAVE), dim3(WAVE), 0, s, sk, st, b.xp, b.hp);
-        if (sk.NP == 8) launch_stage_fused_np<8>(s, sk, st, mm, b, counters, op.stage_rb);
-        else if (sk.NP == 16) launch_stage_fused_np<16>(s, sk, st, mm, b, counters, op.stage_rb);
-        else launch_stage_fused_np<32>(s, sk, st, mm, b, counters, op.stage_rb);
+        if (sk.NP == 8) launch_stage_fused_np<8>(s, sk, st, mm, b, counters);
+        else if (sk.NP == 16) launch_stage_fused_np<16>(s, sk, st, mm, b, counters);
+        else launch_stage_fused_np<32>(s, sk, st, mm, b, counters);
         if (!last && !sk.p_diag)
             hipLaunchKernelGGL(k_precode, dim3(b.U / WAVE, rblk), dim3(WAVE), 0, s, sk, st, b.xp, b.qe, b.qp, b.v,
                                b.u);

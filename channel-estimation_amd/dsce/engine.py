@@ -534,8 +534,8 @@ class Engine:
         min(1e-9, max(1e-11, 4e-16 kappa(R))) max|W|), dev (max |Q' H_hat G - W_thr|),
         wmax (max |W|), rtol (the largest per-slice bar), and the low-rank tap
         operator's fit residual lr_resid (relative), lr (built and kept: eligible; a
-        run uses it with options mic_lr = 1 and mic_net bit 0, see path_info's
-        mic_lr) and lr_ratio (capped bar min(1e-9, max(1e-13, 4e-16 kappa(R))))."""
+        run uses it with option mic_lr = 1, see path_info's mic_lr) and lr_ratio
+        (capped bar min(1e-9, max(1e-13, 4e-16 kappa(R))))."""
         out = (C.c_double * 7)()
         self._chk(self.lib.dsce_structured_check(self.h, int(sid), out), "dsce_structured_check")
         return dict(ratio=out[0], dev=out[1], wmax=out[2], rtol=out[3], lr_resid=out[4], lr=bool(out[5]),

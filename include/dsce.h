@@ -221,7 +221,7 @@ typedef struct {
                                                  IDFT-L per symbol + window sums per residue + DFT-L per symbol
                                                  (k_poly_syn / k_poly_chan / k_poly_ana, option pic_poly) */
 #define DSCE_PATH_WROW3           (1u << 17)  /* unfused W contraction of 32-row blocks as one GEMM per row tile,
-                                                 B = hP v_c (k_wrow3, option wrow) */
+                                                 B = hP v_c (k_wrow3) */
 
 /* Jakes kernels (dsce_jakes_info out6[0]) */
 #define DSCE_JAKES_NONE      0   /* no realisation formed yet                                        */
@@ -413,8 +413,8 @@ int dsce_jakes_info(dsce_ctx* ctx, int32_t* out6);
  * selects a real fallback, reached by the parity tests):
  *   xcd (XCD-aware work order), fuse_stage (MMSE stage in the contraction's
  *   epilogue), pic_chain (3: perfect-CSI IC chain by FFT where the scheme's G / Q
- *   allow it, 0: two banded passes per iteration), pfuse, stage_split, stage_rb
- *   (4|8|16), noise_fuse, snr_chunk (0 all), jakes_rpw (1|2), wtrim (read by
+ *   allow it, 0: two banded passes per iteration), pfuse, stage_split,
+ *   noise_fuse, snr_chunk (0 all), jakes_rpw (1|2), wtrim (read by
  *   dsce_build_mmse), wcontract_valu (the VALU contraction, also the fallback
  *   without pair tiles), mmse_ic (1: the MMSE branch of an FFT-form OFDM scheme
  *   as y - Q'(H_hat (G v)) + diag(D_hat) v with H_hat = E{H | hP}, every stage in
@@ -435,12 +435,14 @@ int dsce_jakes_info(dsce_ctx* ctx, int32_t* out6);
  *   entry by entry to 1e-12 at dsce_add_scheme, with L = 24 or 48, as an IDFT-L
  *   per symbol, window sums per residue n mod L around the channel, and a DFT-L
  *   per symbol, DSCE_PATH_PIC_POLY, the default; 0: the two banded passes),
- *   wrow (1: the unfused W contraction of 32-row blocks — FBMC, C5 — as one
- *   GEMM per 16-row tile over (column, pilot) with B = hP v_c, no per-tile
- *   epilogue, DSCE_PATH_WROW3; 0: k_wpair3's pair tiles), jakes_grp2 (1, the
+ *   jakes_grp2 (1, the
  *   default: a channel with two non-zero taps forms the Jakes taps of the read
  *   windows with k_jakes_grp2 — both taps per wave, each Philox block drawn
  *   once; 0: k_jakes_grp, one tap per block; r06).
+ * Retired after r06 (no scheme or channel selected their other values;
+ * DSCE_EINVAL): pic_net, mic_net (the DPP form of the chain kernels' 4-point
+ * network; the matrix-core form is the only one), stage_rb (k_stage_fused runs 8
+ * rows per wave), wrow (32-row blocks always take k_wrow3, DSCE_PATH_WROW3).
  * Retired in r06 (measured neutral in r04 / r05; DSCE_EINVAL): pic_skip (the
  * perfect-CSI fixed-point exit), ic_streams (the chain on a second stream /
  * beside the pilot pass in one launch, k_ic_pair).
@@ -485,9 +487,9 @@ int dsce_kernel_work(dsce_ctx* ctx, const char* kernel, double* flops_per_rep, d
  * The low-rank form of its tap operator (Bv = T Bz, T_k the J0 kernel summed
  * over pilot symbol k's window; option mic_lr): out[4] = max |Bv - T Bz| /
  * max |Bv| of the fit (-1: not attempted), out[5] = 1 if the operator was
- * built and kept (eligible), else 0 — a run uses it only with the options
- * mic_lr = 1 and mic_net bit 0 set, which DSCE_PATH_MIC_LR of dsce_path_info
- * reports after the run — out[6] = the worst slice's deviation over its rounding
+ * built and kept (eligible), else 0 — a run uses it only with the option
+ * mic_lr = 1, which DSCE_PATH_MIC_LR of dsce_path_info reports after the
+ * run — out[6] = the worst slice's deviation over its rounding
  * bar min(1e-9, max(1e-13, 4e-16 ||R||_1 ||pinv(R)||_1)) max |Bv| (the operator
  * is kept iff <= 1). */
 int dsce_structured_check(dsce_ctx* ctx, int32_t scheme_id, double* out7);

@@ -2,7 +2,7 @@
 """Static per-section instruction census of one kernel's IC-iteration loop.
 
   tools/isa.sh builds the device assembly (/tmp/isa/kmc.s); then
-  python3 tools/census_sections.py /tmp/isa/kmc.s k_pic_fftILi2ELi2ELb0ELb1ELb1E [more.s PATTERN ...]
+  python3 tools/census_sections.py /tmp/isa/kmc.s k_pic_fftILi2ELi2ELb0ELb1EE [more.s PATTERN ...]
 
 The loop is every block LLVM annotates "in Loop" (plus its header).  Each
 instruction is attributed to a section by its opcode family:
