@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <functional>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -1552,9 +1553,25 @@ void copy_col(dsce_ctx* c, double* dst, const double2* src, int rows, int stride
 
 int var_of_stage(int stage, int niter) { return (stage == 0 || stage <= niter / 2) ? 0 : 1; }
 
+// Every unit of one scheme (dsce_export_stages): the stage kernels store through
+// TraceK's bulk mode into k's arrays [stage][element][U]; the LS pilot estimates
+// and y_ic of the paths that keep them in per-unit buffers are copied on the
+// device after each stage (the host copies of the single-unit trace); `flush`
+// writes a chunk out after its last stage.  Only that scheme runs, against
+// scratch counters, and its Scheme::path is left as it was.
+struct Bulk {
+    int scheme;
+    TraceK* dev = nullptr;          // device copy of `k`
+    TraceK k{};                     // U > 0: set per chunk
+    double2* hp = nullptr;          // [stage][NP][U]
+    unsigned long long* counters = nullptr;
+    size_t units = 0;               // capacity of the arrays in units
+    std::function<void(int snr0)> flush;
+};
+
 // Realisations [rep0, rep0 + R) with R a multiple of 64; only the first nvalid
 // add to the counters / MSE sums (the rest pad a run's tail to whole waves).
-void run_batch(dsce_ctx* c, uint64_t seed, uint64_t rep0, int R, int nvalid, Trace* tr) {
+void run_batch(dsce_ctx* c, uint64_t seed, uint64_t rep0, int R, int nvalid, Trace* tr, Bulk* bk = nullptr) {
     TraceRange trace_range("dsce batch");
     McBuffers& b = c->buf;
     const Opts& op = c->op;
@@ -1562,6 +1579,8 @@ void run_batch(dsce_ctx* c, uint64_t seed, uint64_t rep0, int R, int nvalid, Tra
     b.R = R;
     b.rvalid = nvalid;
     b.tr = nullptr;
+    b.tr_bulk = 0;
+    unsigned long long* const counters = bk ? bk->counters : c->d_counters;
     {
         Timed t(c, "k_jakes");
         if (c->jk_nsch != c->schemes.size()) update_jakes_chunks(c);
@@ -1570,7 +1589,9 @@ void run_batch(dsce_ctx* c, uint64_t seed, uint64_t rep0, int R, int nvalid, Tra
     }
     const int chunk = snr_chunk(c);
     for (size_t si = 0; si < c->schemes.size(); ++si) {
+        if (bk && bk->scheme != (int)si) continue;
         Scheme& s = *c->schemes[si];
+        const unsigned path_before = s.path;
         s.path = 0;
         MmseK mm{};
         mm.W = s.W;
@@ -1613,16 +1634,37 @@ void run_batch(dsce_ctx* c, uint64_t seed, uint64_t rep0, int R, int nvalid, Tra
             b.tr = tracing ? tr->dev : nullptr;
             const dsce_trace* to = tracing ? tr->out : nullptr;
             const int LK = s.LK, NP = s.d.n_pilots;
+            const size_t U = (size_t)b.U;
+            if (bk) {
+                // all-ones bytes = NaN / -1: "formed by no kernel of the path"
+                if (U > bk->units) throw ApiError(DSCE_EINVAL, "run_batch: bulk staging too small");
+                const size_t ns = (size_t)c->niter + 1, nd = (size_t)s.d.n_data;
+                bk->k.U = b.U;
+                DSCE_HIP_CHECK(hipMemcpyAsync(bk->dev, &bk->k, sizeof(TraceK), hipMemcpyHostToDevice, c->stream));
+                DSCE_HIP_CHECK(hipMemsetAsync(bk->k.yest, 0xff, ns * LK * U * sizeof(double2), c->stream));
+                DSCE_HIP_CHECK(hipMemsetAsync(bk->k.hest, 0xff, ns * LK * U * sizeof(double2), c->stream));
+                DSCE_HIP_CHECK(hipMemsetAsync(bk->hp, 0xff, ns * NP * U * sizeof(double2), c->stream));
+                DSCE_HIP_CHECK(hipMemsetAsync(bk->k.dec_e, 0xff, ns * nd * U * sizeof(int), c->stream));
+                DSCE_HIP_CHECK(hipMemsetAsync(bk->k.dec_p, 0xff, ns * nd * U * sizeof(int), c->stream));
+                b.tr = bk->dev;
+                b.tr_bulk = 1;
+            }
+            // device copy of a per-unit buffer into stage st of a bulk array (the host's copy_col of a trace)
+            auto bulk_copy = [&](double2* dst, const double2* src, int st, int rows) {
+                DSCE_HIP_CHECK(hipMemcpyAsync(dst + (size_t)st * rows * U, src, (size_t)rows * U * sizeof(double2),
+                                              hipMemcpyDeviceToDevice, c->stream));
+            };
             {
                 Timed t(c, "rx_front");
                 s.path |= launch_rx_front(c->stream, op, s.k, c->ch, c->d_pn, seed, rep0, b);
             }
+            if (bk) bulk_copy(bk->k.yest, b.y, 0, LK);          // stage 0: y_ic = y
             if (to && to->y) copy_col(c, to->y, b.y, LK, b.U, tunit);
             if (to && to->h_perfect) copy_col(c, to->h_perfect, b.h, LK, R, tr->lane);
             // FFT-form OFDM: the perfect-CSI branch is one k_pic_fft with its
             // stage 0, the MMSE branch k_mic_pilot + k_mic_data, every stage each
             if (pfuse && mmse_stages_ok(op, s.k, mm, c->ch, b, c->niter)) {
-                PerfectDetectArgs pd{c->d_counters, (int)si, 0, c->niter + 1, c->nsnr, 0, s.k.slI, s.k.slQ};
+                PerfectDetectArgs pd{counters, (int)si, 0, c->niter + 1, c->nsnr, 0, s.k.slI, s.k.slQ};
                 // the low-rank tap operator (both passes or neither: the data pass
                 // reads the pilot pass's Z instead of its LS pilots)
                 const bool lr = op.mic_lr && s.Bz;
@@ -1647,7 +1689,12 @@ void run_batch(dsce_ctx* c, uint64_t seed, uint64_t rep0, int R, int nvalid, Tra
                 if (to && to->hp_stages)
                     for (int st = 0; st <= c->niter; ++st)
                         copy_col(c, to->hp_stages + (size_t)2 * st * NP, b.hpa + (size_t)st * NP * b.U, NP, b.U, tunit);
+                if (bk) {
+                    for (int st = 0; st <= c->niter; ++st) bulk_copy(bk->hp, b.hpa + (size_t)st * NP * U, st, NP);
+                    bk->flush(s0);
+                }
                 b.tr = nullptr;
+                b.tr_bulk = 0;
                 continue;
             }
             // Otherwise one launch group per stage.  With the perfect-CSI branch
@@ -1665,7 +1712,7 @@ void run_batch(dsce_ctx* c, uint64_t seed, uint64_t rep0, int R, int nvalid, Tra
             for (int it = 0; it <= c->niter; ++it) {
                 if (it == 1 && chain) {
                     Timed t(c, "perfect_ic");
-                    PerfectDetectArgs pd{c->d_counters, (int)si, 1, c->niter + 1, c->nsnr, 0, s.k.slI, s.k.slQ};
+                    PerfectDetectArgs pd{counters, (int)si, 1, c->niter + 1, c->nsnr, 0, s.k.slI, s.k.slQ};
                     s.path |= launch_perfect_chain(c->stream, op, s.k, c->ch, b, &pd, c->niter);
                 }
                 if (it > 0 && mfuse) {
@@ -1674,17 +1721,18 @@ void run_batch(dsce_ctx* c, uint64_t seed, uint64_t rep0, int R, int nvalid, Tra
                         launch_pilot_pre(c->stream, s.k, mm, var_of_stage(it - 1, c->niter), b, hp_prev, hp_cur);
                     }
                     if (to && to->hp_stages) copy_col(c, to->hp_stages + (size_t)2 * it * NP, hp_cur, NP, b.U, tunit);
+                    if (bk) bulk_copy(bk->hp, hp_cur, it, NP);
                     {
                         // the contraction with the stage in its epilogue
                         Timed t(c, "k_wcontract");
                         s.path |= launch_mmse_fused(c->stream, op, s.k, mm, var_of_stage(it - 1, c->niter),
                                                     var_of_stage(it, c->niter), it, c->niter, it == c->niter, b,
-                                                    hp_prev, hp_cur, c->d_counters, (int)si);
+                                                    hp_prev, hp_cur, counters, (int)si);
                     }
                     std::swap(hp_prev, hp_cur);
                     if (!chain) {
                         Timed t(c, "perfect_ic");
-                        PerfectDetectArgs pd{c->d_counters, (int)si, it, c->niter + 1, c->nsnr, it == c->niter,
+                        PerfectDetectArgs pd{counters, (int)si, it, c->niter + 1, c->nsnr, it == c->niter,
                                              s.k.slI, s.k.slQ};
                         s.path |= launch_perfect_ic(c->stream, op, s.k, c->ch, b, pfuse ? &pd : nullptr);
                     }
@@ -1696,9 +1744,10 @@ void run_batch(dsce_ctx* c, uint64_t seed, uint64_t rep0, int R, int nvalid, Tra
                         s.path |= launch_wcontract(c->stream, op, s.k, mm, var_of_stage(it - 1, c->niter), b);
                     }
                     if (to && to->yest_stages) copy_col(c, to->yest_stages + (size_t)2 * it * LK, b.yest, LK, b.U, tunit);
+                    if (bk) bulk_copy(bk->k.yest, b.yest, it, LK);
                     if (!chain) {
                         Timed t(c, "perfect_ic");
-                        PerfectDetectArgs pd{c->d_counters, (int)si, it, c->niter + 1, c->nsnr, it == c->niter,
+                        PerfectDetectArgs pd{counters, (int)si, it, c->niter + 1, c->nsnr, it == c->niter,
                                              s.k.slI, s.k.slQ};
                         s.path |= launch_perfect_ic(c->stream, op, s.k, c->ch, b, pfuse ? &pd : nullptr);
                         if (to && to->yperf_stages && !pfuse)
@@ -1708,12 +1757,16 @@ void run_batch(dsce_ctx* c, uint64_t seed, uint64_t rep0, int R, int nvalid, Tra
                 {
                     Timed t(c, "k_stage");
                     s.path |= launch_stage(c->stream, op, s.k, mm, it, var_of_stage(it, c->niter), c->niter,
-                                           it == c->niter, b, c->d_counters, (int)si, !(pfuse && it > 0));
+                                           it == c->niter, b, counters, (int)si, !(pfuse && it > 0));
                 }
                 if (to && to->hp_stages) copy_col(c, to->hp_stages + (size_t)2 * it * NP, b.hp, NP, b.U, tunit);
+                if (bk) bulk_copy(bk->hp, b.hp, it, NP);
             }
+            if (bk) bk->flush(s0);
             b.tr = nullptr;
+            b.tr_bulk = 0;
         }
+        if (bk) s.path = path_before;
     }
     DSCE_HIP_CHECK(hipGetLastError());
 }
@@ -2535,6 +2588,150 @@ int dsce_export(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, ui
     API_END
 }
 
+// Bulk per-stage export (ABI 10): run_batch for one scheme with the stage kernels
+// in TraceK's bulk mode (struct Bulk), k_export_stages after each SNR chunk.
+// Scratch counters, no MSE sums, Scheme::path restored.  A batch is cut into
+// sub-batches of whole waves so that the bulk arrays stay within option
+// export_stage_mb (every realisation is its own Philox streams: the cut does not
+// show).  On a multi-device handle the handle itself is member 0.
+int dsce_export_stages(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, uint64_t n_rep, uint32_t flags,
+                       const dsce_export_stages_out* out) {
+    TraceRange trace_range("dsce export stages");
+    API_BEGIN
+    check_ctx(ctx);
+    if (!ctx->chan_set) throw ApiError(DSCE_ESTATE, "dsce_set_channel first");
+    if (ctx->nsnr <= 0) throw ApiError(DSCE_ESTATE, "dsce_set_snr first");
+    if (ctx->schemes.empty()) throw ApiError(DSCE_ESTATE, "no scheme added");
+    Scheme& s = get_scheme(ctx, id);
+    if (!out) throw ApiError(DSCE_EINVAL, "dsce_export_stages: null out");
+    if (flags & ~(uint32_t)(DSCE_EXPORT_F32 | DSCE_EXPORT_DEVICE))
+        throw ApiError(DSCE_EINVAL, "dsce_export_stages: unknown flag");
+    // fields in k_export_stages' order
+    void* dst[5] = {out->hp_ls, out->h_est, out->y_ic, out->dec_est, out->dec_perf};
+    bool any = false;
+    for (void* p : dst) any = any || p;
+    if (!any) throw ApiError(DSCE_EINVAL, "dsce_export_stages: no field requested");
+    if (!(s.mmse_ready && s.Wd))
+        throw ApiError(DSCE_ESTATE, "dsce_export_stages: dsce_build_mmse first (or dsce_set_interpolation with n_iter 0)");
+    if (s.interp && ctx->niter > 0)
+        throw ApiError(DSCE_ESTATE, "dsce_export_stages: interference-cancellation iterations need the MMSE estimator "
+                                    "(n_iter must be 0 with an interpolation estimator)");
+    const bool f32 = (flags & DSCE_EXPORT_F32) != 0, to_device = (flags & DSCE_EXPORT_DEVICE) != 0;
+    if (to_device)
+        for (void* p : dst) {
+            if (!p) continue;
+            hipPointerAttribute_t at{};
+            const hipError_t e = hipPointerGetAttributes(&at, p);
+            if (e != hipSuccess) (void)hipGetLastError();
+            if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != ctx->device)
+                throw ApiError(DSCE_EINVAL, "dsce_export_stages: DSCE_EXPORT_DEVICE with a pointer that is not device "
+                                            "memory of the context's GPU");
+        }
+    const int LK = s.LK, NP = s.d.n_pilots, ND = s.d.n_data, nsnr = ctx->nsnr, S = ctx->niter + 1;
+    const size_t csz = f32 ? sizeof(float2) : sizeof(double2);
+    const int flen[5] = {NP, LK, LK, ND, ND};
+    const size_t esz[5] = {csz, csz, csz, sizeof(int32_t), sizeof(int32_t)};
+    size_t per_rep[5];
+    for (int f = 0; f < 5; ++f) per_rep[f] = (size_t)nsnr * S * flen[f];
+    // the bulk trace arrays of one unit: hP, diag(D_hat), y_ic and both decisions of every stage
+    const int chunk = snr_chunk(ctx);
+    const size_t unit_bytes = (size_t)S * (((size_t)NP + 2 * (size_t)LK) * sizeof(double2) + 2 * (size_t)ND * sizeof(int));
+    const size_t bound = (size_t)ctx->op.export_stage_mb << 20;
+    const size_t waves = std::max<size_t>(1, bound / (unit_bytes * 64 * (size_t)chunk));
+    const int rsub = (int)std::min<size_t>((size_t)(ctx->batch + 63) / 64, waves) * 64;
+    std::vector<void*> tmp;
+    auto talloc = [&](size_t bytes) {
+        void* p;
+        DSCE_HIP_CHECK(hipMalloc(&p, bytes));
+        tmp.push_back(p);
+        return p;
+    };
+    try {
+        Bulk bk;
+        bk.scheme = id;
+        bk.units = (size_t)rsub * chunk;
+        bk.k.LK = LK;
+        bk.k.ND = ND;
+        bk.k.unit = 0;
+        bk.k.yperf = nullptr;
+        bk.k.yest = (double2*)talloc(bk.units * S * LK * sizeof(double2));
+        bk.k.hest = (double2*)talloc(bk.units * S * LK * sizeof(double2));
+        bk.k.dec_e = (int*)talloc(bk.units * S * ND * sizeof(int));
+        bk.k.dec_p = (int*)talloc(bk.units * S * ND * sizeof(int));
+        bk.hp = (double2*)talloc(bk.units * S * NP * sizeof(double2));
+        bk.dev = (TraceK*)talloc(sizeof(TraceK));
+        const size_t ncount = ctx->schemes.size() * 4 * (size_t)nsnr * S;
+        bk.counters = (unsigned long long*)talloc(ncount * sizeof(unsigned long long));
+        DSCE_HIP_CHECK(hipMemsetAsync(bk.counters, 0, ncount * sizeof(unsigned long long), ctx->stream));
+        uint64_t done = 0;
+        while (done < n_rep) {
+            const uint64_t left = n_rep - done;
+            const int R = (int)std::min<uint64_t>((uint64_t)rsub, (left + 63) / 64 * 64);
+            const int nvalid = (int)std::min<uint64_t>((uint64_t)R, left);
+            ensure_buffers(ctx, ctx->batch);
+            ctx->buf.mse_err = ctx->buf.mse_pow = nullptr;
+            ExportStagesK ek{};
+            ek.row0 = to_device ? (long long)done : 0;
+            if (to_device) {
+                for (int f = 0; f < 5; ++f) ek.out[f] = dst[f];
+            } else {
+                // one sub-batch of every requested field, each 256-byte aligned
+                size_t off[5], total = 0;
+                for (int f = 0; f < 5; ++f) {
+                    off[f] = total;
+                    if (dst[f]) total += ((size_t)nvalid * per_rep[f] * esz[f] + 255) / 256 * 256;
+                }
+                if (total > ctx->exp_stage_bytes) {
+                    if (ctx->exp_stage) {
+                        DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+                        DSCE_HIP_CHECK(hipFree(ctx->exp_stage));
+                    }
+                    ctx->exp_stage = nullptr;
+                    ctx->exp_stage_bytes = 0;
+                    DSCE_HIP_CHECK(hipMalloc(&ctx->exp_stage, total));
+                    ctx->exp_stage_bytes = total;
+                }
+                for (int f = 0; f < 5; ++f) ek.out[f] = dst[f] ? (char*)ctx->exp_stage + off[f] : nullptr;
+            }
+            ek.src[0] = bk.hp;
+            ek.src[1] = bk.k.hest;
+            ek.src[2] = bk.k.yest;
+            ek.src[3] = bk.k.dec_e;
+            ek.src[4] = bk.k.dec_p;
+            for (int f = 0; f < 5; ++f) {
+                ek.len[f] = flen[f];
+                ek.tiles[f] = dst[f] ? (flen[f] + EXPORT_TILE - 1) / EXPORT_TILE : 0;
+            }
+            ek.S = S;
+            ek.R = R;
+            ek.nsnr = nsnr;
+            ek.rvalid = nvalid;
+            bk.flush = [&](int snr0) {
+                ek.U = ctx->buf.U;
+                ek.snr0 = snr0;
+                Timed t(ctx, "k_export_stages");
+                launch_export_stages(ctx->stream, ek, f32);
+            };
+            run_batch(ctx, seed, first_rep + done, R, nvalid, nullptr, &bk);
+            if (!to_device)
+                for (int f = 0; f < 5; ++f)
+                    if (dst[f])
+                        DSCE_HIP_CHECK(hipMemcpyAsync((char*)dst[f] + (size_t)done * per_rep[f] * esz[f], ek.out[f],
+                                                      (size_t)nvalid * per_rep[f] * esz[f], hipMemcpyDeviceToHost,
+                                                      ctx->stream));
+            done += (uint64_t)nvalid;
+        }
+        DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (ctx->timing) collect_timing(ctx);
+    } catch (...) {
+        (void)hipStreamSynchronize(ctx->stream);
+        for (void* p : tmp) (void)hipFree(p);
+        throw;
+    }
+    for (void* p : tmp) DSCE_HIP_CHECK(hipFree(p));
+    API_END
+}
+
 int dsce_bits_per_rep(dsce_ctx* ctx, int32_t id, int64_t* bits2) {
     API_BEGIN
     check_ctx(ctx);
@@ -3034,7 +3231,7 @@ int dsce_fp64_mfma_peak(dsce_ctx* ctx, double* tflops) {
 // Kernel-selection options (Opts); the defaults are the measured-best path.
 #define DSCE_OPTIONS(X)                                                                                  \
     X(xcd) X(fuse_stage) X(pic_chain) X(pfuse) X(stage_split) X(noise_fuse) \
-    X(snr_chunk) X(jakes_rpw) X(wtrim) X(wcontract_valu) X(mmse_ic) X(jakes_win) X(txrx_fft) X(snr_base) X(jakes_mom) X(realise_win) X(tx_rows) X(mic_lr) X(pic_poly) X(jakes_grp2)
+    X(snr_chunk) X(jakes_rpw) X(wtrim) X(wcontract_valu) X(mmse_ic) X(jakes_win) X(txrx_fft) X(snr_base) X(jakes_mom) X(realise_win) X(tx_rows) X(mic_lr) X(pic_poly) X(jakes_grp2) X(export_stage_mb)
 
 static int set_option_one(dsce_ctx* ctx, const char* name, int64_t value) {
     API_BEGIN
@@ -3057,6 +3254,7 @@ static int set_option_one(dsce_ctx* ctx, const char* name, int64_t value) {
                                     "(k_pic_chain, k_pic_mfma) were retired in r03");
     if (n == "snr_base" && (value < 0 || value > 255)) throw ApiError(DSCE_EINVAL, "snr_base: 0..255");
     if (n == "snr_base") check_noise_streams(ctx, value, ctx->nsnr, max_noise_slot(ctx));
+    if (n == "export_stage_mb" && value < 1) throw ApiError(DSCE_EINVAL, "export_stage_mb: >= 1 (MiB)");
     if (value < -1 || value > 1 << 20) throw ApiError(DSCE_EINVAL, "option value out of range");
     *slot = (int)value;
     API_END

@@ -37,6 +37,8 @@ struct Opts {
     int jakes_mom = 2;        // Jakes taps of the read windows: 2 = Taylor anchors over groups of windows
                               // (k_jakes_grp), 1 = one anchor per window (k_jakes_mom), 0 = recurrence;
                               // each where its truncation is below rounding, else the next lower
+    int export_stage_mb = 1024; // dsce_export_stages: bound in MiB on the bulk trace arrays of one sub-batch
+                              // (whole 64-realisation waves; one wave is the floor)
 };
 
 // Kernels a scheme's last dsce_run / dsce_trace_unit_ex went through
@@ -65,15 +67,39 @@ enum : unsigned {
 // Per-stage trace of one unit (dsce_trace_unit_ex): every kernel that forms one
 // of these quantities for unit `unit` of the traced scheme writes it here.
 // Device arrays, stage-major: [stage][LK] / [stage][ND].
+// Bulk mode (U > 0, dsce_export_stages): every unit of the chunk stores, into
+// element-major arrays [stage][LK][U] / [stage][ND][U] with the unit fastest, so
+// a wave's stores of one element are contiguous.  trace_hit / trace_ix are the
+// only readers of unit and U.
 struct TraceK {
     int unit;
     int LK, ND;
     double2* yest;     // y_est of stage s (the MMSE IC input y - (D_hat - diag) v), s >= 1
-    double2* yperf;    // y_perf of stage s (perfect-CSI IC), s >= 1
+    double2* yperf;    // y_perf of stage s (perfect-CSI IC), s >= 1; null: not wanted (bulk)
     double2* hest;     // diag(D_hat) of stage s
     int* dec_e;        // detected symbol index per data symbol, MMSE branch
     int* dec_p;        // perfect-CSI branch
+    int U;             // 0: the single unit `unit`; else the chunk's unit count (bulk).  Last, so the
+                       // single-unit code of the kernels dsce_run shares with the trace reads the offsets it did
 };
+// Does `unit` store, and where: e = stage * LK + row (or stage * ND + symbol) is
+// the single-unit index, e * U + unit the bulk one.  The <BULK> forms are for
+// kernels whose one instance serves dsce_run too (k_stage_fused, k_wpair3): their
+// bulk mode is an instance of its own and the other keeps its code.
+__device__ __forceinline__ bool trace_hit(const TraceK* t, int unit) { return t->U > 0 || unit == t->unit; }
+__device__ __forceinline__ size_t trace_ix(const TraceK* t, size_t e, int unit) {
+    return t->U > 0 ? e * (size_t)t->U + (size_t)unit : e;
+}
+template <bool BULK>
+__device__ __forceinline__ bool trace_hit(const TraceK* t, int unit) {
+    if constexpr (BULK) return true;
+    else return unit == t->unit;
+}
+template <bool BULK>
+__device__ __forceinline__ size_t trace_ix(const TraceK* t, size_t e, int unit) {
+    if constexpr (BULK) return e * (size_t)t->U + (size_t)unit;
+    else return e;
+}
 
 struct McBuffers {
     int R;            // repetitions per batch (multiple of 64)
@@ -116,6 +142,7 @@ struct McBuffers {
     double* mse_err;  // null, or [scheme][snr][stage] sums of |h_hat - h|^2 (dsce_enable_mse)
     double* mse_pow;  // [scheme][snr] sums of |h|^2
     const TraceK* tr; // device trace of one unit (null: not tracing this scheme / chunk)
+    int tr_bulk;      // tr is in bulk mode (TraceK::U > 0): the launchers pick the bulk instances
 };
 
 struct MmseK {
@@ -256,6 +283,22 @@ struct ExportK {
     int tiles[6];
 };
 void launch_export(hipStream_t s, const ExportK& a, bool f32);
+
+// Bulk per-stage export of one batch and SNR chunk after its last stage
+// (k_export_stages; dsce_export_stages): the transpose of the bulk trace arrays
+// [stage][element][U] to [rep][snr][stage][element].  Fields in the order hp_ls,
+// h_est, y_ic (complex), dec_est, dec_perf (int32); tiles[f] = 32-element tiles
+// per stage of field f (0: not requested).  Output element of realisation rl
+// (< rvalid), SNR index snr, stage s: (((row0 + rl) nsnr + snr) S + s) len + element.
+struct ExportStagesK {
+    const void* src[5];       // [S][len][U]: double2 (fields 0-2) / int (3, 4); NaN / -1 where nothing was formed
+    int len[5];               // NP, LK, LK, ND, ND
+    int S, R, U, snr0, nsnr, rvalid;
+    long long row0;
+    void* out[5];
+    int tiles[5];
+};
+void launch_export_stages(hipStream_t s, const ExportStagesK& a, bool f32);
 
 // setup (correlation matrices and MMSE estimator)
 struct SetupArgs {

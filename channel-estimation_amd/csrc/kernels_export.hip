@@ -129,4 +129,57 @@ void launch_export(hipStream_t s, const ExportK& a, bool f32) {
     launch_tiles(s, rest, f32);
 }
 
+// k_export_stages — the stage-aware sibling of k_export (dsce_export_stages): the
+// sources are the bulk trace arrays [stage][element][U] that the stage kernels
+// filled (TraceK bulk mode), so every field is a pure move.  One block = 64
+// consecutive units x one 32-element tile of one (field, stage); the same two
+// phases and the same odd-stride LDS tile as k_export.  NaN / -1 entries (formed
+// by no kernel of the path) go through as they are.
+template <bool F32>
+__global__ void __launch_bounds__(256) k_export_stages(ExportStagesK a) {
+    __shared__ double2 tile[64 * XS];
+    int job = blockIdx.y, field = 0;
+    while (field < 4 && job >= a.tiles[field] * a.S) job -= a.tiles[field++] * a.S;
+    const int stage = job / a.tiles[field], e0 = (job % a.tiles[field]) * XT;
+    const int first = blockIdx.x * 64;                    // first unit of the block (one SNR point: R % 64 == 0)
+    const int snr = a.snr0 + first / a.R;
+    const int rl0 = first % a.R;
+    const int nv = min(64, a.rvalid - rl0);               // realisations of the group that are written
+    if (nv <= 0) return;                                  // a wave of tail padding (block-uniform)
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int len = a.len[field];
+    const bool cplx = field < 3;
+    int* itile = (int*)tile;
+    const size_t base = (size_t)stage * len;
+    if (cplx) {
+        const double2* __restrict__ src = (const double2*)a.src[field];
+        for (int e = w; e < XT; e += 4)
+            if (e0 + e < len) tile[lane * XS + e] = src[(base + e0 + e) * a.U + first + lane];
+    } else {
+        const int* __restrict__ src = (const int*)a.src[field];
+        for (int e = w; e < XT; e += 4)
+            if (e0 + e < len) itile[lane * XS + e] = src[(base + e0 + e) * a.U + first + lane];
+    }
+    __syncthreads();
+    // lane = element: 32 consecutive elements of one realisation per half wave
+    const int e = threadIdx.x & (XT - 1);
+    if (e0 + e >= len) return;
+    for (int u = threadIdx.x / XT; u < nv; u += 256 / XT) {
+        const long long row = a.row0 + rl0 + u;
+        const size_t idx = ((size_t)(row * a.nsnr + snr) * a.S + stage) * (size_t)len + (size_t)(e0 + e);
+        if (cplx) export_store(a.out[field], idx, tile[u * XS + e], F32);
+        else ((int*)a.out[field])[idx] = itile[u * XS + e];
+    }
+}
+
+void launch_export_stages(hipStream_t s, const ExportStagesK& a, bool f32) {
+    int ntile = 0;
+    for (int f = 0; f < 5; ++f) ntile += a.tiles[f] * a.S;
+    if (!ntile) return;
+    const dim3 grid(a.U / 64, ntile);
+    if (f32) hipLaunchKernelGGL((k_export_stages<true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_export_stages<false>), grid, dim3(256), 0, s, a);
+}
+
 }  // namespace dsce

@@ -1241,6 +1241,9 @@ struct StorePerfectDetect {
         c0 = 0;
         c1 = 0;
     }
+    // BULK (the methods' last template argument): TraceK's bulk mode, every unit
+    // stores; StorePerfectDetectBulk below calls those forms, so a kernel has one
+    // instance per mode and the instance dsce_run launches keeps its code
     __device__ __forceinline__ void operator()(int row, int lane, double2 acc) {
         if (row_data[row] < 0) return;
         detect(row, lane, acc, u[(size_t)row * U + lane]);
@@ -1258,7 +1261,7 @@ struct StorePerfectDetect {
                                            const double2 (&ur)[RBN]) {
         rows_impl<RBN, true>(row0, nrows, lane, acc, ur);
     }
-    template <int RBN, bool UREG>
+    template <int RBN, bool UREG, bool BULK = false>
     __device__ __forceinline__ void rows_impl(int row0, int nrows, int lane, const double2 (&acc)[RBN],
                                               const double2 (&ur)[RBN]) {
         const int rl = lane % R;
@@ -1291,9 +1294,9 @@ struct StorePerfectDetect {
                 const int ne = __popc((unsigned)(dp ^ tx[k]));
                 c0 += ne;
                 c1 += cn[k] ? ne : 0;
-                if (tr && lane == tr->unit) {
-                    tr->yperf[(size_t)stage * tr->LK + row0 + r] = rr;
-                    tr->dec_p[(size_t)stage * tr->ND + dd[k]] = dp;
+                if (tr && trace_hit<BULK>(tr, lane)) {
+                    if constexpr (!BULK) tr->yperf[(size_t)stage * tr->LK + row0 + r] = rr;   // not exported in bulk
+                    tr->dec_p[trace_ix<BULK>(tr, (size_t)stage * tr->ND + dd[k], lane)] = dp;
                 }
                 if (!last) {
                     double2 av = make_double2(0.0, 0.0);
@@ -1304,6 +1307,7 @@ struct StorePerfectDetect {
         }
     }
     // y_perf = y - acc + h u of one row, sliced, counted, re-precoded into u
+    template <bool BULK = false>
     __device__ __forceinline__ void detect(int row, int lane, double2 acc, double2 uv) {
         const size_t i = (size_t)row * U + lane;
         const int rl = lane % R;
@@ -1318,9 +1322,9 @@ struct StorePerfectDetect {
         const int ne = __popc((unsigned)(dp ^ (int)sidx[(size_t)d * R + rl]));
         c0 += ne;
         c1 += row_cons[row] ? ne : 0;
-        if (tr && lane == tr->unit) {
-            tr->yperf[(size_t)stage * tr->LK + row] = r;
-            tr->dec_p[(size_t)stage * tr->ND + d] = dp;
+        if (tr && trace_hit<BULK>(tr, lane)) {
+            if constexpr (!BULK) tr->yperf[(size_t)stage * tr->LK + row] = r;
+            tr->dec_p[trace_ix<BULK>(tr, (size_t)stage * tr->ND + d, lane)] = dp;
         }
         if (!last) {
             double2 av = make_double2(0.0, 0.0);
@@ -1338,6 +1342,26 @@ struct StorePerfectDetect {
             const int v = l ? t1 : t0;
             if (v) atomicAdd(&counters[i0], (unsigned long long)v);
         }
+    }
+};
+
+// StorePerfectDetect with tr in bulk mode (dsce_export_stages): the same data,
+// the entry points k_band / k_poly_ana call routed to the BULK forms
+struct StorePerfectDetectBulk : StorePerfectDetect {
+    StorePerfectDetectBulk() = default;
+    __host__ __device__ StorePerfectDetectBulk(const StorePerfectDetect& o) : StorePerfectDetect(o) {}
+    __device__ __forceinline__ void operator()(int row, int lane, double2 acc) {
+        if (row_data[row] < 0) return;
+        detect<true>(row, lane, acc, u[(size_t)row * U + lane]);
+    }
+    template <int RBN>
+    __device__ __forceinline__ void rows(int row0, int nrows, int lane, const double2 (&acc)[RBN]) {
+        rows_impl<RBN, false, true>(row0, nrows, lane, acc, acc);
+    }
+    template <int RBN>
+    __device__ __forceinline__ void rows_u(int row0, int nrows, int lane, const double2 (&acc)[RBN],
+                                           const double2 (&ur)[RBN]) {
+        rows_impl<RBN, true, true>(row0, nrows, lane, acc, ur);
     }
 };
 
@@ -1962,7 +1986,7 @@ __device__ __forceinline__ void pic_fft_body(const SchemeK& sk, const BandOrder&
         for (int a = 0; a < 6; ++a) {
             const bool data = (dmask >> a) & 1;
             ncnt += __umul24(__popc((unsigned)(dp[a] ^ (int)((txp[a >> 2] >> (8 * (a & 3))) & 0xffu))), cweight(a));
-            if (TRACE && data && unit == o.tr->unit) o.tr->dec_p[(size_t)(rdc[4 * a + r] >> 1)] = dp[a];
+            if (TRACE && data && trace_hit(o.tr, unit)) o.tr->dec_p[trace_ix(o.tr, (size_t)(rdc[4 * a + r] >> 1), unit)] = dp[a];
         }
         reprecode(dp);
         cntl[w][0] = wave_sum_dpp(rl < o.rvalid ? ncnt : 0);
@@ -2025,10 +2049,10 @@ __device__ __forceinline__ void pic_fft_body(const SchemeK& sk, const BandOrder&
             const double2 xa = x[p6(a)], hh = hc[a];
             fI[a] = fma(-xa.x, hh.x, fma(xa.y, hh.y, yh[a].x));
             fQ[a] = fma(fma(-xa.x, hh.y, fma(-xa.y, hh.x, yh[a].y)), rq, o.ofQ);
-            if (TRACE && ((dmask >> a) & 1) && unit == o.tr->unit) {
+            if (TRACE && ((dmask >> a) & 1) && o.tr->yperf && trace_hit(o.tr, unit)) {
                 const int row = row0 + 4 * a + r;
                 const double2 yv = o.y[(size_t)row * U + unit];
-                o.tr->yperf[(size_t)it * o.tr->LK + row] = c_sub(yv, make_double2(xa.x / cs, xa.y / cs));
+                o.tr->yperf[trace_ix(o.tr, (size_t)it * o.tr->LK + row, unit)] = c_sub(yv, make_double2(xa.x / cs, xa.y / cs));
             }
         }
         // a decision exactly on a mid-point (measure zero): the smallest symbol
@@ -2038,7 +2062,8 @@ __device__ __forceinline__ void pic_fft_body(const SchemeK& sk, const BandOrder&
         for (int a = 0; a < 6; ++a) {
             const bool data = (dmask >> a) & 1;
             ncnt += __umul24(__popc((unsigned)(dp[a] ^ (int)((txp[a >> 2] >> (8 * (a & 3))) & 0xffu))), cweight(a));
-            if (TRACE && data && unit == o.tr->unit) o.tr->dec_p[(size_t)it * o.tr->ND + (rdc[4 * a + r] >> 1)] = dp[a];
+            if (TRACE && data && trace_hit(o.tr, unit))
+                o.tr->dec_p[trace_ix(o.tr, (size_t)it * o.tr->ND + (rdc[4 * a + r] >> 1), unit)] = dp[a];
         }
         if (it < niter) reprecode(dp);                           // the last iteration's decisions are only counted
         cntl[w][it] = wave_sum_dpp(rl < o.rvalid ? ncnt : 0);    // uniform: every lane writes the same word
@@ -2512,11 +2537,11 @@ __device__ __forceinline__ void mic2_stages(const SchemeK& sk, const Mic2Args& m
         for (int a = 0; a < 6; ++a) {
             const bool data = (dmask >> a) & 1;
             ncnt += __umul24(__popc((unsigned)(dp[a] ^ (int)((txp[a >> 2] >> (8 * (a & 3))) & 0xffu))), cweight(a));
-            if (TRACE && unit == o.tr->unit) {
+            if (TRACE && trace_hit(o.tr, unit)) {
                 const int row = row0 + 4 * a + r;
-                o.tr->yest[(size_t)s * o.tr->LK + row] = ye[a];
-                o.tr->hest[(size_t)s * o.tr->LK + row] = hd[a];
-                if (data) o.tr->dec_e[(size_t)s * o.tr->ND + (rdc[4 * a + r] >> 1)] = dp[a];
+                o.tr->yest[trace_ix(o.tr, (size_t)s * o.tr->LK + row, unit)] = ye[a];
+                o.tr->hest[trace_ix(o.tr, (size_t)s * o.tr->LK + row, unit)] = hd[a];
+                if (data) o.tr->dec_e[trace_ix(o.tr, (size_t)s * o.tr->ND + (rdc[4 * a + r] >> 1), unit)] = dp[a];
             }
         }
         if (s == ma.niter) {
@@ -3499,11 +3524,14 @@ unsigned launch_perfect_ic(hipStream_t s, const Opts& op, const SchemeK& sk, con
     o.tr = b.tr;
     o.stage = pd->stage;
     const size_t lds = 256 * sizeof(double2) + sizeof(SlicerLds);
+    const bool bulk = b.tr && b.tr_bulk;
     if (poly) {
-        launch_poly_ana(s, sk, pa, o, lds);
+        if (bulk) launch_poly_ana(s, sk, pa, StorePerfectDetectBulk(o), lds);
+        else launch_poly_ana(s, sk, pa, o, lds);
         return PATH_PIC_POLY;
     }
-    launch_pass2_nt(s, sk, ch, b, ord, o, lds);
+    if (bulk) launch_pass2_nt(s, sk, ch, b, ord, StorePerfectDetectBulk(o), lds);
+    else launch_pass2_nt(s, sk, ch, b, ord, o, lds);
     return PATH_PIC_PASSES;
 }
 
@@ -3590,7 +3618,7 @@ struct FuseArgs {
     int rvalid;                    // realisations of the batch that count (McBuffers::rvalid)
 };
 
-template <int RBP, int NKS, bool FUSE>
+template <int RBP, int NKS, bool FUSE, bool BULK = false>
 __device__ __forceinline__ void wpair3_body(const PairBand& P, const double* __restrict__ W3, long long wp_elems,
                                             int var, int nsnr, int snr0, int R, int U,
                                             const double2* __restrict__ hp, const double2* v,
@@ -3824,10 +3852,10 @@ __device__ __forceinline__ void wpair3_body(const PairBand& P, const double* __r
         const int ne = dc >= 0 ? __popc((unsigned)(de ^ (int)((ftx[k >> 2] >> (8 * (k & 3))) & 0xffu))) : 0;
         cnt[0] += ne;
         cnt[1] += (dc & 1) ? ne : 0;
-        if (fa.tr && valid && unit == fa.tr->unit) {
-            fa.tr->yest[(size_t)fa.stage * fa.tr->LK + row] = ye;
-            fa.tr->hest[(size_t)fa.stage * fa.tr->LK + row] = he;
-            if (dc >= 0) fa.tr->dec_e[(size_t)fa.stage * fa.tr->ND + (dc >> 1)] = de;
+        if (fa.tr && valid && trace_hit<BULK>(fa.tr, unit)) {
+            fa.tr->yest[trace_ix<BULK>(fa.tr, (size_t)fa.stage * fa.tr->LK + row, unit)] = ye;
+            fa.tr->hest[trace_ix<BULK>(fa.tr, (size_t)fa.stage * fa.tr->LK + row, unit)] = he;
+            if (dc >= 0) fa.tr->dec_e[trace_ix<BULK>(fa.tr, (size_t)fa.stage * fa.tr->ND + (dc >> 1), unit)] = de;
         }
         if (!fa.last && dc >= 0) {
             double2 av = make_double2(0.0, 0.0);
@@ -3846,6 +3874,14 @@ __global__ void __launch_bounds__(256)
              const double2* __restrict__ hp, const double2* v, const double2* __restrict__ y,
              double2* __restrict__ yest, SchemeK sk, FuseArgs fa) {
     wpair3_body<RBP, NKS, FUSE>(P, W3, wp_elems, var, nsnr, snr0, R, U, hp, v, y, yest, sk, fa);
+}
+
+// the fused stage with every unit stored (TraceK bulk mode, dsce_export_stages)
+__global__ void __launch_bounds__(256)
+    k_wpair3_bulk(PairBand P, const double* __restrict__ W3, long long wp_elems, int var, int nsnr, int snr0, int R,
+                  int U, const double2* __restrict__ hp, const double2* v, const double2* __restrict__ y,
+                  double2* __restrict__ yest, SchemeK sk, FuseArgs fa) {
+    wpair3_body<24, 4, true, true>(P, W3, wp_elems, var, nsnr, snr0, R, U, hp, v, y, yest, sk, fa);
 }
 
 // The unfused W contraction of 32-row blocks (FBMC, C5) as ONE GEMM per row
@@ -4033,8 +4069,12 @@ unsigned launch_mmse_fused(hipStream_t s, const Opts& op, const SchemeK& sk, con
     fa.scheme = scheme_index;
     fa.rvalid = b.rvalid;
     const dim3 grid(b.U / 64, mm.Pb.nblk);
-    hipLaunchKernelGGL((k_wpair3<24, 4, true>), grid, dim3(256), 0, s, mm.Pb, mm.Wp3, mm.wp_elems, var_prev, mm.nsnr,
-                       b.snr0, b.R, b.U, hp_prev, b.v, b.y, b.yest, sk, fa);
+    if (b.tr && b.tr_bulk)
+        hipLaunchKernelGGL(k_wpair3_bulk, grid, dim3(256), 0, s, mm.Pb, mm.Wp3, mm.wp_elems, var_prev, mm.nsnr, b.snr0,
+                           b.R, b.U, hp_prev, b.v, b.y, b.yest, sk, fa);
+    else
+        hipLaunchKernelGGL((k_wpair3<24, 4, true>), grid, dim3(256), 0, s, mm.Pb, mm.Wp3, mm.wp_elems, var_prev,
+                           mm.nsnr, b.snr0, b.R, b.U, hp_prev, b.v, b.y, b.yest, sk, fa);
     return PATH_WPAIR3_FUSED;
 }
 
@@ -4118,9 +4158,11 @@ struct StageArgs {
 // LS pilot estimates k_ls wrote (r04: each row block recomputed the NP complex
 // LS divisions itself, and wrote h_hat, which nothing reads, to HBM);
 // grid (U/64, ceil(LK/RB)).
-__global__ void __launch_bounds__(64) k_ls_hest(SchemeK sk, StageArgs st, const double2* __restrict__ Wd,
-                                                const double2* __restrict__ h, const double2* __restrict__ hp,
-                                                double2* __restrict__ e_est, double2* __restrict__ e_perf) {
+// (BULK: TraceK's bulk mode, every unit stores: k_ls_hest_bulk / k_detect_bulk below)
+template <bool BULK>
+__device__ __forceinline__ void ls_hest_body(const SchemeK& sk, const StageArgs& st, const double2* __restrict__ Wd,
+                                             const double2* __restrict__ h, const double2* __restrict__ hp,
+                                             double2* __restrict__ e_est, double2* __restrict__ e_perf) {
     extern __shared__ double2 shp[];                     // [NP][64], each lane its own column
     const int unit = blockIdx.x * WAVE + threadIdx.x;
     const int snr = st.snr0 + (blockIdx.x * WAVE) / st.R;
@@ -4136,7 +4178,8 @@ __global__ void __launch_bounds__(64) k_ls_hest(SchemeK sk, StageArgs st, const 
         for (int p = 0; p < sk.NP; ++p) c_fma(acc, wd[(size_t)c * sk.NP + p], shp[p * WAVE + threadIdx.x]);
         const size_t i = (size_t)c * U + unit;
         const double2 hv = h[(size_t)c * R + rl];
-        if (st.tr && unit == st.tr->unit) st.tr->hest[(size_t)st.stage * st.tr->LK + c] = acc;
+        if (st.tr && trace_hit<BULK>(st.tr, unit))
+            st.tr->hest[trace_ix<BULK>(st.tr, (size_t)st.stage * st.tr->LK + c, unit)] = acc;
         e_est[i] = c_div(st.ysrc_e[i], acc);
         e_perf[i] = c_div(st.ysrc_p[i], hv);
         if (st.mse_err) {
@@ -4147,67 +4190,20 @@ __global__ void __launch_bounds__(64) k_ls_hest(SchemeK sk, StageArgs st, const 
     }
     if (st.mse_err) flush_mse(me, mp, st.mse_err, st.mse_pow, st.scheme, st.nsnr, snr, st.nstage, st.stage, rl < st.rvalid);
 }
+__global__ void __launch_bounds__(64) k_ls_hest(SchemeK sk, StageArgs st, const double2* __restrict__ Wd,
+                                                const double2* __restrict__ h, const double2* __restrict__ hp,
+                                                double2* __restrict__ e_est, double2* __restrict__ e_perf) {
+    ls_hest_body<false>(sk, st, Wd, h, hp, e_est, e_perf);
+}
+__global__ void __launch_bounds__(64) k_ls_hest_bulk(SchemeK sk, StageArgs st, const double2* __restrict__ Wd,
+                                                     const double2* __restrict__ h, const double2* __restrict__ hp,
+                                                     double2* __restrict__ e_est, double2* __restrict__ e_perf) {
+    ls_hest_body<true>(sk, st, Wd, h, hp, e_est, e_perf);
+}
 
 // (2) data-symbol decisions and bit-error counts, grid (U/64, ceil(ND/32)).
 static constexpr int DET_CHUNK = 32;
-__global__ void __launch_bounds__(64) k_detect(SchemeK sk, StageArgs st, const uint16_t* __restrict__ sidx,
-                                               const double2* __restrict__ e_est, const double2* __restrict__ e_perf,
-                                               uint16_t* __restrict__ qe, uint16_t* __restrict__ qp,
-                                               unsigned long long* __restrict__ counters) {
-    __shared__ SlicerLds slt;
-    const bool lds_slicer = sk.nI <= 16 && sk.nQ <= 16;
-    if (lds_slicer) slicer_load(slt, sk, threadIdx.x, WAVE);
-    __syncthreads();
-    const double sI = sk.slI, sQ = sk.slQ;
-    const int unit = blockIdx.x * WAVE + threadIdx.x;
-    const int snr = st.snr0 + (blockIdx.x * WAVE) / st.R;
-    const int rl = unit % st.R;
-    const int U = st.U, R = st.R;
-    const int i0 = blockIdx.y * DET_CHUNK;
-    const int i1 = min(sk.ND, i0 + DET_CHUNK);
-    int cnt[4] = {0, 0, 0, 0};
-    for (int csi = 0; csi < 2; ++csi) {
-        const double2* __restrict__ e = csi == 0 ? e_est : e_perf;
-        uint16_t* __restrict__ qo = csi == 0 ? qe : qp;
-        for (int i = i0; i < i1; ++i) {
-            double2 z;
-            if (sk.despread) {                                  // x = P' (y ./ h), script:436 / :520
-                const int row = sk.NP + i;
-                double2 acc = make_double2(0.0, 0.0);
-                // entries in groups of 4, every load of a group issued before its
-                // products (one global round trip per group instead of per entry)
-                const int j0 = sk.ph_ptr[row], j1 = sk.ph_ptr[row + 1];
-                for (int jb = j0; jb < j1; jb += 4) {
-                    double2 ev[4], pv[4];
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const int jj = min(jb + g, j1 - 1);
-                        pv[g] = jb + g < j1 ? sk.ph_val[jj] : make_double2(0.0, 0.0);
-                        ev[g] = e[(size_t)sk.ph_col[jj] * U + unit];
-                    }
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) c_fma(acc, pv[g], ev[g]);
-                }
-                z = acc;
-                z = sk.real_detect ? make_double2(z.x / sk.data_div, 0.0)
-                                   : make_double2(z.x / sk.data_div, z.y / sk.data_div);
-            } else {                                            // x(data positions) ./ sqrt(DPR)
-                z = e[(size_t)sk.data_pos[i] * U + unit];
-                z = sk.real_detect ? make_double2(z.x / sk.data_div, 0.0)
-                                   : make_double2(z.x / sk.data_div, z.y / sk.data_div);
-            }
-            const int d = lds_slicer ? slice_fast(slt, sk.nI, sk.nQ, z, sI, sQ) : slice(sk, z);
-            const int tx = sidx[(size_t)i * R + rl];
-            const int ne = __popc((unsigned)(d ^ tx));
-            if (st.tr && unit == st.tr->unit) (csi ? st.tr->dec_p : st.tr->dec_e)[(size_t)st.stage * st.tr->ND + i] = d;
-            cnt[csi * 2 + 0] += ne;
-            if (sk.considered[i]) cnt[csi * 2 + 1] += ne;
-            if (!st.last) qo[(size_t)i * U + unit] = (uint16_t)d;
-        }
-    }
-    flush_counts(cnt, counters, (((size_t)st.scheme * 4) * st.nsnr + snr) * st.nstage + st.stage,
-                 (size_t)st.nsnr * st.nstage, 2, rl < st.rvalid);
-}
+// (k_detect and its bulk twin: stage_kernels.inc below, one text under two names)
 
 // (3) re-precoding of the quantised decisions for the next IC iteration:
 // v = P [xP; Q(x_est)], u = P [xP; Q(x_perf)] (script:482-484, :541-543);
@@ -4279,177 +4275,21 @@ __global__ void __launch_bounds__(64) k_ls(SchemeK sk, StageArgs st, const doubl
 // contraction uses a W band with a zero diagonal, so nothing else reads it.
 // Flat grid, row block fastest (the blocks of one unit group share hP in L2).
 static constexpr int STAGE_RB = 8;                         // rows per wave of k_stage_fused
-template <int NPT, bool PERF, bool MSE>
-__global__ void __launch_bounds__(256) k_stage_fused(SchemeK sk, StageArgs st, int nrb, const double2* __restrict__ Wd,
-                                                     const double2* __restrict__ xp,
-                                                     const uint16_t* __restrict__ sidx,
-                                                     const double2* __restrict__ h,
-                                                     const double2* __restrict__ hp, double2* __restrict__ hest,
-                                                     uint16_t* __restrict__ qe, uint16_t* __restrict__ qp,
-                                                     double2* __restrict__ v, double2* __restrict__ u,
-                                                     unsigned long long* __restrict__ counters) {
-    constexpr int RB = STAGE_RB;
-    __shared__ double2 sym[256];
-    __shared__ SlicerLds slt;
-    __shared__ double2 shp[NPT * 64];                      // the block's 64 units' LS pilot estimates
-    __shared__ double2 swd[4 * RB * NPT];                  // diag(W) rows of the block (broadcast reads)
-    // Block = 64 units x 4*RB rows (wave w: rows [4 RB blk + w RB, +RB)); the LS
-    // pilot estimates of the 64 units go through LDS once for the 4 waves.
-    // Work order: row block fastest, then SNR point, then 64-realisation group,
-    // so the blocks sharing hP (same units) and h (same realisations) run close
-    // together; with xcd_order each XCD (block b runs on XCD b % 8) walks its own
-    // contiguous range of that order, keeping the reuse inside one L2.
-    int L = blockIdx.x;
-    if (st.xcd_order) L = xcd_remap(L, gridDim.x);
-    const int rbk = L % nrb;
-    int ug = L / nrb;
-    if (st.xcd_order) {
-        const int nchunk = st.U / st.R, rgs = st.R >> 6;
-        ug = (ug % nchunk) * rgs + ug / nchunk;
-    }
-    // wave index made provably uniform so Wd / row tables become scalar loads
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int U = st.U, R = st.R;
-    const int unit = ug * 64 + lane;
-    const int snr = st.snr0 + (ug * 64) / R;
-    const int rl = unit % R;
-    const int r0 = (rbk * 4 + wv) * RB;
-    const int nr = max(0, min(RB, sk.LK - r0));
-    // every per-row operand of the wave is requested up front (rows past the
-    // end / pilot rows read a valid dummy), so their latency overlaps diag(D_hat)
-    double2 ye[RB], yp[RB], hh[RB];
-    int tx[RB];
-    const bool same_y = st.ysrc_p == st.ysrc_e;
-#pragma unroll
-    for (int r = 0; r < RB; ++r) {
-        const int row = r < nr ? r0 + r : 0;
-        const int i = sk.row_data[row];
-        const size_t ix = (size_t)row * U + unit;
-        ye[r] = st.ysrc_e[ix];
-        tx[r] = sidx[(size_t)(i > 0 ? i : 0) * R + rl];
-        if (PERF) yp[r] = same_y ? ye[r] : st.ysrc_p[ix];
-        if (PERF || MSE) hh[r] = h[(size_t)row * R + rl];
-    }
-    // per-row scalars of the wave's rows, requested together (no dependent chains)
-    int rdat[RB], rcons[RB], rpcol[RB];
-    double2 rpval[RB];
-#pragma unroll
-    for (int r = 0; r < RB; ++r) {
-        const int row = r < nr ? r0 + r : 0;
-        rdat[r] = sk.row_data[row];
-        rcons[r] = sk.row_cons[row];
-        rpcol[r] = sk.row_pcol[row];
-        rpval[r] = sk.row_pval[row];
-    }
-    {
-        // LDS staging: hP of the 64 units, diag(W) rows of the block, tables;
-        // every global load is issued before the first LDS write
-        constexpr int NW = (4 * RB * NPT + 255) / 256;
-        double2 hv[NPT / 4], wv_[NW];
-#pragma unroll
-        for (int k = 0; k < NPT / 4; ++k) {
-            const int i = threadIdx.x + 256 * k;
-            hv[k] = hp[(size_t)(i >> 6) * U + ug * 64 + (i & 63)];
-        }
-        const int rb0 = rbk * 4 * RB;
-        const double2* __restrict__ wdb = Wd + ((size_t)st.var * st.nsnr + snr) * (size_t)sk.LK * NPT;
-#pragma unroll
-        for (int k = 0; k < NW; ++k) {
-            const int i = threadIdx.x + 256 * k;
-            const int row = rb0 + i / NPT;
-            wv_[k] = (i < 4 * RB * NPT && row < sk.LK) ? wdb[(size_t)rb0 * NPT + i] : make_double2(0.0, 0.0);
-        }
-        stage_tables<256>(sym, slt, sk, threadIdx.x);
-#pragma unroll
-        for (int k = 0; k < NPT / 4; ++k) shp[threadIdx.x + 256 * k] = hv[k];
-#pragma unroll
-        for (int k = 0; k < NW; ++k)
-            if (threadIdx.x + 256 * k < 4 * RB * NPT) swd[threadIdx.x + 256 * k] = wv_[k];
-    }
-    __syncthreads();
-    if (nr == 0) return;
-    const double2* __restrict__ wds = swd + wv * RB * NPT;
-    double2 acc[RB];
-#pragma unroll
-    for (int r = 0; r < RB; ++r) acc[r] = make_double2(0.0, 0.0);
-#pragma unroll
-    for (int p = 0; p < NPT; ++p) {
-        const double2 hv = shp[p * 64 + lane];
-#pragma unroll
-        for (int r = 0; r < RB; ++r)
-            if (r < nr) c_fma(acc[r], wds[r * NPT + p], hv);
-    }
-    if (MSE) {
-        double me = 0.0, mp = 0.0;
-#pragma unroll
-        for (int r = 0; r < RB; ++r)
-            if (r < nr) {
-                const double dx = acc[r].x - hh[r].x, dy = acc[r].y - hh[r].y;
-                me += dx * dx + dy * dy;
-                mp += hh[r].x * hh[r].x + hh[r].y * hh[r].y;
-            }
-        flush_mse(me, mp, st.mse_err, st.mse_pow, st.scheme, st.nsnr, snr, st.nstage, st.stage, rl < st.rvalid);
-    }
-    const double idd = 1.0 / sk.data_div;
-    const double sI = sk.slI, sQ = sk.slQ;
-    int cnt[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int r = 0; r < RB; ++r) {
-        if (r < nr) {
-            const int row = r0 + r;
-            const size_t ix = (size_t)row * U + unit;
-            const bool traced = st.tr && unit == st.tr->unit;
-            if (traced) st.tr->hest[(size_t)st.stage * st.tr->LK + row] = acc[r];
-            const int i = rdat[r];
-            if (i >= 0) {
-                const double2 ze = c_div1(ye[r], acc[r]);
-                const int de = slice_fast(slt, sk.nI, sk.nQ, sk.real_detect ? make_double2(ze.x * idd, 0.0)
-                                                             : make_double2(ze.x * idd, ze.y * idd), sI, sQ);
-                const int ne = __popc((unsigned)(de ^ tx[r]));
-                const int cons = rcons[r];
-                cnt[0] += ne;
-                cnt[1] += cons ? ne : 0;
-                int dp = 0;
-                if (PERF) {
-                    const double2 zp = c_div1(yp[r], hh[r]);
-                    dp = slice_fast(slt, sk.nI, sk.nQ, sk.real_detect ? make_double2(zp.x * idd, 0.0)
-                                                      : make_double2(zp.x * idd, zp.y * idd), sI, sQ);
-                    const int np_ = __popc((unsigned)(dp ^ tx[r]));
-                    cnt[2] += np_;
-                    cnt[3] += cons ? np_ : 0;
-                }
-                if (traced) {
-                    st.tr->dec_e[(size_t)st.stage * st.tr->ND + i] = de;
-                    if (PERF) st.tr->dec_p[(size_t)st.stage * st.tr->ND + i] = dp;
-                }
-                if (!st.last) {
-                    if (sk.p_diag) {
-                        const double2 pv = rpval[r];
-                        double2 av = make_double2(0.0, 0.0), au = av;
-                        if (rpcol[r] >= 0) {
-                            c_fma(av, pv, sym[de]);
-                            c_fma(au, pv, sym[dp]);
-                        }
-                        v[ix] = av;
-                        if (PERF) u[ix] = au;
-                    } else {
-                        const size_t qi = (size_t)i * U + unit;
-                        qe[qi] = (uint16_t)de;
-                        qp[qi] = (uint16_t)dp;
-                    }
-                }
-            } else if (!st.last && sk.p_diag && st.stage == 0) {   // pilot / empty row: constant P xP
-                const int kc = rpcol[r];
-                double2 av = make_double2(0.0, 0.0);
-                if (kc >= 0) c_fma(av, rpval[r], xp[(size_t)kc * R + rl]);
-                v[ix] = av;
-                u[ix] = av;
-            }
-        }
-    }
-    flush_counts(cnt, counters, (((size_t)st.scheme * 4) * st.nsnr + snr) * st.nstage + st.stage,
-                 (size_t)st.nsnr * st.nstage, PERF ? 2 : 1, rl < st.rvalid);
-}
+#define STAGE_FUSED_KERNEL k_stage_fused
+#define STAGE_DETECT_KERNEL k_detect
+#define STAGE_FUSED_BULK false
+#include "stage_kernels.inc"
+#undef STAGE_FUSED_KERNEL
+#undef STAGE_DETECT_KERNEL
+#undef STAGE_FUSED_BULK
+// every unit stores its trace (dsce_export_stages; instantiated without MSE sums)
+#define STAGE_FUSED_KERNEL k_stage_fused_bulk
+#define STAGE_DETECT_KERNEL k_detect_bulk
+#define STAGE_FUSED_BULK true
+#include "stage_kernels.inc"
+#undef STAGE_FUSED_KERNEL
+#undef STAGE_DETECT_KERNEL
+#undef STAGE_FUSED_BULK
 
 template <int NPT>
 static void launch_stage_fused_np(hipStream_t s, const SchemeK& sk, const StageArgs& st, const MmseK& mm, McBuffers& b,
@@ -4458,11 +4298,18 @@ static void launch_stage_fused_np(hipStream_t s, const SchemeK& sk, const StageA
 #define LAUNCH_SF(PERFV, MSEV)                                                                                \
     hipLaunchKernelGGL((k_stage_fused<NPT, PERFV, MSEV>), dim3(ug * nrb), dim3(256), 0, s, sk, st, nrb, mm.Wd, b.xp, \
                        b.sidx, b.h, b.hp, b.hest, b.qe, b.qp, b.v, b.u, counters)
-    if (st.mse_err && st.perfect) LAUNCH_SF(true, true);
+#define LAUNCH_SFB(PERFV)                                                                                     \
+    hipLaunchKernelGGL((k_stage_fused_bulk<NPT, PERFV, false>), dim3(ug * nrb), dim3(256), 0, s, sk, st, nrb, mm.Wd, b.xp, \
+                       b.sidx, b.h, b.hp, b.hest, b.qe, b.qp, b.v, b.u, counters)
+    if (b.tr && b.tr_bulk) {                                // dsce_export_stages: no MSE sums
+        if (st.perfect) LAUNCH_SFB(true);
+        else LAUNCH_SFB(false);
+    } else if (st.mse_err && st.perfect) LAUNCH_SF(true, true);
     else if (st.mse_err) LAUNCH_SF(false, true);
     else if (st.perfect) LAUNCH_SF(true, false);
     else LAUNCH_SF(false, false);
 #undef LAUNCH_SF
+#undef LAUNCH_SFB
 }
 
 static bool stage_fused_ok(const Opts& op, const SchemeK& sk) {
@@ -4507,10 +4354,11 @@ unsigned launch_stage(hipStream_t s, const Opts& op, const SchemeK& sk, const Mm
         return PATH_STAGE_FUSED;
     }
     hipLaunchKernelGGL(k_ls, dim3(b.U / WAVE), dim3(WAVE), 0, s, sk, st, b.xp, b.hp);
-    hipLaunchKernelGGL(k_ls_hest, dim3(b.U / WAVE, rblk), dim3(WAVE), (size_t)sk.NP * WAVE * sizeof(double2), s, sk,
-                       st, mm.Wd, b.h, b.hp, b.e, b.e2);
-    hipLaunchKernelGGL(k_detect, dim3(b.U / WAVE, (sk.ND + DET_CHUNK - 1) / DET_CHUNK), dim3(WAVE), 0, s, sk, st,
-                       b.sidx, b.e, b.e2, b.qe, b.qp, counters);
+    const bool bulk = b.tr && b.tr_bulk;
+    hipLaunchKernelGGL(bulk ? k_ls_hest_bulk : k_ls_hest, dim3(b.U / WAVE, rblk), dim3(WAVE),
+                       (size_t)sk.NP * WAVE * sizeof(double2), s, sk, st, mm.Wd, b.h, b.hp, b.e, b.e2);
+    hipLaunchKernelGGL(bulk ? k_detect_bulk : k_detect, dim3(b.U / WAVE, (sk.ND + DET_CHUNK - 1) / DET_CHUNK),
+                       dim3(WAVE), 0, s, sk, st, b.sidx, b.e, b.e2, b.qe, b.qp, counters);
     if (!last)
         hipLaunchKernelGGL(k_precode, dim3(b.U / WAVE, rblk), dim3(WAVE), 0, s, sk, st, b.xp, b.qe, b.qp, b.v, b.u);
     return PATH_STAGE_SPLIT;

@@ -15,7 +15,14 @@ Arrays of a shard (n = realisations of the shard): y, hp_ls, h_est
 [n][n_snr][LK | NP], h [n][LK], xp [n][NP] (complex64 or complex128), sym
 [n][ND] int32; metadata: config, scheme, snr_db, pn_time, seed, first_rep,
 n_rep, dtype, pilot_pos, data_pos, symbols (the constellation), kappa, data_div,
-L, K, abi."""
+L, K, abi.
+
+--stages adds what the iterative interference cancellation forms, per stage
+s = 0 (one-tap) .. n_iter (dsce_export_stages; --n-iter, default 4 as in the
+script): hp_ls_stages [n][n_snr][S][NP], h_est_stages and y_ic_stages
+[n][n_snr][S][LK], the detected symbol indices dec_est / dec_perf
+[n][n_snr][S][ND] int32 of the MMSE and the perfect-CSI branch, and n_iter in
+the metadata.  bit_errors(sym, dec) counts their bit errors per (SNR, stage)."""
 from __future__ import annotations
 
 import argparse
@@ -27,6 +34,32 @@ import numpy as np
 
 DTYPES = ("complex64", "complex128")
 FIELDS = ("y", "hp_ls", "h_est", "h", "xp", "sym")
+# shard name of each dsce_export_stages field (--stages)
+STAGE_NAMES = {"hp_ls": "hp_ls_stages", "h_est": "h_est_stages", "y_ic": "y_ic_stages", "dec_est": "dec_est",
+               "dec_perf": "dec_perf"}
+STAGE_ARRAYS = tuple(STAGE_NAMES.values())
+
+
+def bit_errors(sym, dec, considered=None):
+    """Bit errors per (SNR, stage) of the decisions dec [n][n_snr][S][ND] against
+    the transmitted symbol indices sym [n][ND]: popcount(sym ^ dec) summed over
+    realisations and data symbols (a symbol index is its bit label), over the
+    symbols with considered[i] != 0 when `considered` [ND] is given (the
+    scheme's no-edge flags).  int64 [n_snr][S]."""
+    sym = np.asarray(sym)
+    dec = np.asarray(dec)
+    if dec.ndim != 4 or sym.shape != (dec.shape[0], dec.shape[3]):
+        raise ValueError("sym must be [n][ND] and dec [n][n_snr][S][ND]")
+    if (dec < 0).any():
+        raise ValueError("dec holds entries that no kernel formed (-1)")
+    x = (sym[:, None, None, :].astype(np.int64) ^ dec.astype(np.int64)).astype(np.uint32)
+    nb = np.zeros(x.shape, dtype=np.int64)
+    while x.any():
+        nb += x & 1
+        x = x >> 1
+    if considered is not None:
+        nb = nb * (np.asarray(considered).reshape(1, 1, 1, -1) != 0)
+    return nb.sum(axis=(0, 3))
 
 
 def shard_path(prefix, index):
@@ -46,7 +79,7 @@ def write_shard(path, arrays, meta):
     file, then os.replace).  meta must carry first_rep and n_rep."""
     n = int(meta["n_rep"])
     for k, a in arrays.items():
-        if k not in FIELDS:
+        if k not in FIELDS and k not in STAGE_ARRAYS:
             raise ValueError("unknown field %r" % k)
         if a.shape[0] != n:
             raise ValueError("field %s holds %d realisations, the shard %d" % (k, a.shape[0], n))
@@ -105,6 +138,9 @@ def parser():
     ap.add_argument("--batch", type=int, default=8192, help="realisations per device batch")
     ap.add_argument("--dtype", choices=DTYPES, default="complex64")
     ap.add_argument("--no-mmse", action="store_true", help="skip dsce_build_mmse and the h_est field")
+    ap.add_argument("--stages", action="store_true",
+                    help="add the per-stage IC arrays (hp_ls_stages, h_est_stages, y_ic_stages, dec_est, dec_perf)")
+    ap.add_argument("--n-iter", type=int, default=None, help="IC iterations of --stages (default 4)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", required=True, help="shard prefix: writes PREFIX-00000.npz ...")
     return ap
@@ -114,11 +150,18 @@ def main(argv=None):
     a = parser().parse_args(argv)
     if a.reps < 1 or a.shard_reps < 1 or a.first_rep < 0:
         raise SystemExit("--reps and --shard-reps must be >= 1, --first-rep >= 0")
+    if a.n_iter is not None and not a.stages:
+        raise SystemExit("--n-iter belongs to --stages")
+    if a.stages and a.no_mmse:
+        raise SystemExit("--stages needs the MMSE estimator (drop --no-mmse)")
+    if a.n_iter is not None and a.n_iter < 0:
+        raise SystemExit("--n-iter must be >= 0")
 
     from dsce.configs import build_setup
     from dsce.engine import ABI_VERSION, build_engine, gpu_tx
 
-    S = build_setup(a.config, schemes=(a.scheme,), snr_db=a.snr_db, tx=gpu_tx(a.device))
+    kw = dict(n_iter=4 if a.n_iter is None else a.n_iter) if a.stages else {}
+    S = build_setup(a.config, schemes=(a.scheme,), snr_db=a.snr_db, tx=gpu_tx(a.device), **kw)
     sc = S.schemes[a.scheme]
     eng = build_engine(S, device=a.device, batch=max(64, min(a.batch, a.reps)), mmse=not a.no_mmse)
     fields = tuple(f for f in FIELDS if not (a.no_mmse and f == "h_est"))
@@ -127,9 +170,14 @@ def main(argv=None):
                 pilot_pos=np.asarray(sc.pilot_pos, dtype=np.int32), data_pos=np.asarray(sc.data_pos, dtype=np.int32),
                 symbols=np.asarray(sc.const.SymbolMapping, dtype=np.complex128).ravel(), kappa=float(sc.kappa),
                 data_div=float(sc.data_div), L=int(S.L), K=int(sc.LK // S.L), abi=int(ABI_VERSION))
+    if a.stages:
+        base["n_iter"] = int(S.n_iter)
     try:
         for i, (first, n) in enumerate(shard_ranges(a.first_rep, a.reps, a.shard_reps)):
             arrays = eng.export(0, a.seed, first, n, fields=fields, dtype=np.dtype(a.dtype))
+            if a.stages:
+                st = eng.export_stages(0, a.seed, first, n, dtype=np.dtype(a.dtype))
+                arrays.update({STAGE_NAMES[f]: v for f, v in st.items()})
             print("wrote", write_shard(shard_path(a.out, i), arrays, dict(base, first_rep=int(first), n_rep=int(n))),
                   flush=True)
     finally:

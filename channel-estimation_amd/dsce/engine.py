@@ -24,16 +24,19 @@ EXPORTED = [
     "dsce_set_noise_slot", "dsce_set_interpolation", "dsce_enable_mse", "dsce_get_mse", "dsce_trace_unit_ex",
     "dsce_scheme_dims", "dsce_path_info", "dsce_set_option", "dsce_get_option", "dsce_fp64_mfma_peak",
     "dsce_kernel_work", "dsce_structured_check", "dsce_create_multi", "dsce_group_info",
-    "dsce_transmission_matrix", "dsce_jakes_info", "dsce_export",
+    "dsce_transmission_matrix", "dsce_jakes_info", "dsce_export", "dsce_export_stages",
 ]
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 # dsce_export flags (include/dsce.h DSCE_EXPORT_*)
 EXPORT_F32 = 1 << 0
 EXPORT_DEVICE = 1 << 1
 # dsce_export fields in the order of dsce_export_out
 EXPORT_FIELDS = ("y", "hp_ls", "h_est", "h", "xp", "sym")
+# dsce_export_stages fields in the order of dsce_export_stages_out
+STAGE_FIELDS = ("hp_ls", "h_est", "y_ic", "dec_est", "dec_perf")
+_STAGE_INT = ("dec_est", "dec_perf")
 
 # dsce_jakes_info kernels (include/dsce.h DSCE_JAKES_*)
 JAKES_KERNELS = {0: "none", 1: "static", 2: "discrete", 3: "full", 4: "win_rec", 5: "win_mom", 6: "win_grp"}
@@ -83,6 +86,11 @@ class Trace(C.Structure):
 class ExportOut(C.Structure):
     _fields_ = [("y", C.c_void_p), ("hp_ls", C.c_void_p), ("h_est", C.c_void_p), ("h", C.c_void_p),
                 ("xp", C.c_void_p), ("sym", C.POINTER(C.c_int32))]
+
+
+class ExportStagesOut(C.Structure):
+    _fields_ = [("hp_ls", C.c_void_p), ("h_est", C.c_void_p), ("y_ic", C.c_void_p),
+                ("dec_est", C.POINTER(C.c_int32)), ("dec_perf", C.POINTER(C.c_int32))]
 
 
 class TxDesc(C.Structure):
@@ -149,6 +157,8 @@ def load_library(path=None):
     lib.dsce_kernel_work.argtypes = [vp, C.c_char_p, dp, dp]
     lib.dsce_structured_check.argtypes = [vp, C.c_int32, dp]
     lib.dsce_export.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(ExportOut)]
+    lib.dsce_export_stages.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                       C.POINTER(ExportStagesOut)]
     for name in EXPORTED:
         fn = getattr(lib, name)
         if name != "dsce_last_error":
@@ -432,6 +442,66 @@ class Engine:
         torch.cuda.current_stream(dev).synchronize()
         self._export(sid, seed, first_rep, n_rep, EXPORT_DEVICE | (EXPORT_F32 if dtype == torch.complex64 else 0),
                      {f: t.data_ptr() for f, t in out.items()})
+        return out
+
+    # -- bulk per-stage export (ABI 10) ------------------------------------------
+    def export_stages_shapes(self, sid, n_rep):
+        """Shapes of dsce_export_stages' arrays for n_rep realisations of scheme sid
+        (S = 1 + n_iter stages)."""
+        d = self.scheme_dims(sid)
+        n, S = int(n_rep), d.n_iter + 1
+        return dict(hp_ls=(n, d.n_snr, S, d.n_pilots), h_est=(n, d.n_snr, S, d.lk), y_ic=(n, d.n_snr, S, d.lk),
+                    dec_est=(n, d.n_snr, S, d.n_data), dec_perf=(n, d.n_snr, S, d.n_data))
+
+    def _export_stages(self, sid, seed, first_rep, n_rep, flags, ptrs):
+        bad = [f for f in ptrs if f not in STAGE_FIELDS]
+        if bad:
+            raise ValueError("unknown stage export field(s) %s (of %s)" % (bad, list(STAGE_FIELDS)))
+        o = ExportStagesOut()
+        for f, p in ptrs.items():
+            setattr(o, f, C.cast(p, C.POINTER(C.c_int32)) if f in _STAGE_INT else p)
+        self._chk(self.lib.dsce_export_stages(self.h, int(sid), int(seed), int(first_rep), int(n_rep), int(flags),
+                                              C.byref(o)), "dsce_export_stages")
+
+    def export_stages(self, sid, seed, first_rep, n_rep, fields=STAGE_FIELDS, dtype=np.complex128):
+        """Per-stage IC data of realisations [first_rep, first_rep + n_rep) of
+        scheme sid (dsce_export_stages) as a dict of NumPy arrays, stage 0 = the
+        one-tap stage, stage i = IC iteration i: hp_ls [n_rep][n_snr][S][NP], h_est
+        and y_ic [n_rep][n_snr][S][LK] (dtype complex128, or complex64:
+        DSCE_EXPORT_F32), dec_est / dec_perf [n_rep][n_snr][S][ND] int32 (the
+        detected symbol indices of the MMSE and the perfect-CSI branch).  From the
+        kernels of run() on its path; realisation rep is realisation rep of run()
+        and of export() with the same seed.  NaN / -1: formed by no kernel of the
+        path."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.complex128), np.dtype(np.complex64)):
+            raise ValueError("export dtype must be complex128 or complex64")
+        shapes = self.export_stages_shapes(sid, n_rep)
+        out = {f: np.zeros(shapes[f], dtype=np.int32 if f in _STAGE_INT else dt) for f in fields}
+        self._export_stages(sid, seed, first_rep, n_rep, EXPORT_F32 if dt == np.dtype(np.complex64) else 0,
+                            {f: a.ctypes.data for f, a in out.items()})
+        return out
+
+    def export_stages_torch(self, sid, seed, first_rep, n_rep, fields=STAGE_FIELDS, dtype=None, device=None):
+        """export_stages() into torch tensors on the context's GPU, written by the
+        export kernel itself (DSCE_EXPORT_DEVICE); see export_torch for dtype,
+        device and the import order of torch and the engine."""
+        import torch
+        dtype = torch.complex128 if dtype is None else dtype
+        if dtype not in (torch.complex128, torch.complex64):
+            raise ValueError("export_stages_torch dtype must be torch.complex128 or torch.complex64")
+        if not torch.cuda.is_available():
+            raise DsceError("export_stages_torch: torch sees no HIP device in this process; import torch before the "
+                            "first dsce.engine.Engine is created so that both use one HIP runtime")
+        if device is None:
+            device = self.group_info()[0][0]
+        shapes = self.export_stages_shapes(sid, n_rep)
+        dev = "cuda:%d" % int(device)
+        out = {f: torch.empty(shapes[f], dtype=torch.int32 if f in _STAGE_INT else dtype, device=dev) for f in fields}
+        torch.cuda.current_stream(dev).synchronize()
+        self._export_stages(sid, seed, first_rep, n_rep,
+                            EXPORT_DEVICE | (EXPORT_F32 if dtype == torch.complex64 else 0),
+                            {f: t.data_ptr() for f, t in out.items()})
         return out
 
     # -- engine state ------------------------------------------------------------

@@ -32,6 +32,10 @@
  *   dsce_export           <- the workspace arrays of the loop body, per realisation:
  *                            y, hP_LS, h_hat (stage 0), h, xP and the data symbols
  *                                                               script:355-368, :388-393, :406-428
+ *   dsce_export_stages    <- the same for the IC loop, per realisation and stage:
+ *                            hP_LS, h_hat, y after interference cancellation and
+ *                            the detected symbols of both CSI branches
+ *                                                               script:412-453, :482-548
  *
  * Conventions
  *  - Return 0 on success, a negative DSCE_E* code on failure; the message is
@@ -75,6 +79,8 @@
  *
  * ABI 9 adds dsce_export (dsce_export_out, DSCE_EXPORT_*): per-realisation data
  * in bulk.  Every ABI 8 entry point is unchanged.
+ * ABI 10 adds dsce_export_stages (dsce_export_stages_out): the per-stage IC
+ * data of every realisation in bulk.  Every ABI 9 entry point is unchanged.
  */
 #ifndef DSCE_H
 #define DSCE_H
@@ -85,7 +91,7 @@
 extern "C" {
 #endif
 
-#define DSCE_ABI_VERSION 9
+#define DSCE_ABI_VERSION 10
 
 #define DSCE_OK 0
 #define DSCE_EINVAL -1      /* bad argument / shape */
@@ -395,6 +401,40 @@ typedef struct {               /* every pointer optional; realisation-major, C o
  * of the context's GPU.  With dsce_enable_timing the kernel is "k_export". */
 int dsce_export(dsce_ctx* ctx, int32_t scheme_id, uint64_t seed, uint64_t first_rep, uint64_t n_rep,
                 uint32_t flags, const dsce_export_out* out);
+
+/* ---- bulk per-stage export (ABI 10) -------------------------------------- */
+typedef struct {            /* every pointer optional; C order, element fastest; S = 1 + n_iter */
+    void*    hp_ls;     /* [n_rep][n_snr][S][NP]  LS pilot estimates of stage s       script:412-414, :487-489 */
+    void*    h_est;     /* [n_rep][n_snr][S][LK]  diag(D_hat_s), W / W0 per the i <= NrIter/2 switch
+                                                                                     script:417-428, :492-515 */
+    void*    y_ic;      /* [n_rep][n_snr][S][LK]  y - (D_hat_(s-1) - diag) v_(s-1); stage 0 = y
+                                                                                     script:482-484 */
+    int32_t* dec_est;   /* [n_rep][n_snr][S][ND]  detected symbol index, MMSE branch   script:431, :527 */
+    int32_t* dec_perf;  /* [n_rep][n_snr][S][ND]  detected symbol index, perfect CSI   script:453, :548 */
+} dsce_export_stages_out;
+
+/* Realisations [first_rep, first_rep + n_rep) of one scheme, every SNR point and
+ * every stage (one-tap + n_iter IC iterations) of both CSI branches: the Philox
+ * streams and the kernels of dsce_run with the context's options, on the kernel
+ * path dsce_run takes for the scheme, so realisation `rep` is realisation `rep`
+ * of a run and of dsce_export with the same seed.  The stage kernels store every
+ * unit into element-major staging arrays ([stage][element][unit], the bulk mode
+ * of the per-unit trace), and "k_export_stages" (its name under
+ * dsce_enable_timing) transposes them to the layouts above.  An entry that no
+ * kernel of the path forms is NaN (-1 for the decisions), as in dsce_trace; on
+ * the default OFDM and FBMC paths every entry is formed.  Flags, precision,
+ * destinations and pointer validation are those of dsce_export.  Works batch by
+ * batch and SNR chunk by SNR chunk; a batch is cut into sub-batches of whole
+ * 64-realisation waves so that the staging arrays stay within option
+ * export_stage_mb MiB (default 1024; one wave is the floor), and the result does
+ * not depend on the cut.  Any n_rep >= 0; padding realisations are written
+ * nowhere.  Synchronous.  Nothing is added to the error counters, the MSE sums
+ * or dsce_path_info.  DSCE_ESTATE before channel, SNR points or scheme are set,
+ * and without dsce_build_mmse (an interpolation scheme with n_iter == 0 needs
+ * none).  DSCE_EINVAL for a null out, no field requested, an unknown flag or a
+ * bad device pointer.  On a multi-device handle the export is member 0's. */
+int dsce_export_stages(dsce_ctx* ctx, int32_t scheme_id, uint64_t seed, uint64_t first_rep, uint64_t n_rep,
+                       uint32_t flags, const dsce_export_stages_out* out);
 
 /* ---- engine state ------------------------------------------------------- */
 int dsce_scheme_dims(dsce_ctx* ctx, int32_t scheme_id, dsce_dims* dims);
