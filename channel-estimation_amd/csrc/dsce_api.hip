@@ -2001,6 +2001,7 @@ int dsce_create(int hip_device, dsce_ctx** out) {
     try {
         DSCE_HIP_CHECK(hipSetDevice(hip_device));
         DSCE_HIP_CHECK(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
+        DSCE_HIP_CHECK(hipDeviceGetAttribute(&ctx->op.dev_cus, hipDeviceAttributeMultiprocessorCount, hip_device));
     } catch (const std::exception& e) {
         delete ctx;
         return DSCE_EHIP;
@@ -3231,7 +3232,7 @@ int dsce_fp64_mfma_peak(dsce_ctx* ctx, double* tflops) {
 // Kernel-selection options (Opts); the defaults are the measured-best path.
 #define DSCE_OPTIONS(X)                                                                                  \
     X(xcd) X(fuse_stage) X(pic_chain) X(pfuse) X(stage_split) X(noise_fuse) \
-    X(snr_chunk) X(jakes_rpw) X(wtrim) X(wcontract_valu) X(mmse_ic) X(jakes_win) X(txrx_fft) X(snr_base) X(jakes_mom) X(realise_win) X(tx_rows) X(mic_lr) X(pic_poly) X(jakes_grp2) X(export_stage_mb)
+    X(snr_chunk) X(jakes_rpw) X(wtrim) X(wcontract_valu) X(mmse_ic) X(jakes_win) X(txrx_fft) X(snr_base) X(jakes_mom) X(realise_win) X(tx_rows) X(mic_lr) X(pic_poly) X(jakes_grp2) X(export_stage_mb) X(snr_loop)
 
 static int set_option_one(dsce_ctx* ctx, const char* name, int64_t value) {
     API_BEGIN
@@ -3254,6 +3255,9 @@ static int set_option_one(dsce_ctx* ctx, const char* name, int64_t value) {
                                     "(k_pic_chain, k_pic_mfma) were retired in r03");
     if (n == "snr_base" && (value < 0 || value > 255)) throw ApiError(DSCE_EINVAL, "snr_base: 0..255");
     if (n == "snr_base") check_noise_streams(ctx, value, ctx->nsnr, max_noise_slot(ctx));
+    if (n == "snr_loop" && (value < -1 || value > 1))
+        throw ApiError(DSCE_EINVAL, "snr_loop: 0 (a block per 64 units) | 1 (a block walks its realisations' SNR points) | "
+                                    "-1 (by grid size)");
     if (n == "export_stage_mb" && value < 1) throw ApiError(DSCE_EINVAL, "export_stage_mb: >= 1 (MiB)");
     if (value < -1 || value > 1 << 20) throw ApiError(DSCE_EINVAL, "option value out of range");
     *slot = (int)value;

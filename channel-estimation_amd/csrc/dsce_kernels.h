@@ -37,6 +37,12 @@ struct Opts {
     int jakes_mom = 2;        // Jakes taps of the read windows: 2 = Taylor anchors over groups of windows
                               // (k_jakes_grp), 1 = one anchor per window (k_jakes_mom), 0 = recurrence;
                               // each where its truncation is below rounding, else the next lower
+    int snr_loop = -1;        // k_pic_fft's SNR-loop form (a block walks the chunk's SNR points of its 64
+                              // realisations, the per-realisation prologue once): 1 = wherever it applies,
+                              // 0 = never (a block per 64 units), -1 = where the looped grid still fills
+                              // the device (launch_perfect_chain)
+    int dev_cus = 0;          // not an option: the compute units of the context's device (dsce_create), read
+                              // by snr_loop's rule
     int export_stage_mb = 1024; // dsce_export_stages: bound in MiB on the bulk trace arrays of one sub-batch
                               // (whole 64-realisation waves; one wave is the floor)
 };
@@ -62,6 +68,7 @@ enum : unsigned {
     PATH_MIC_LR = 1u << 15,        // ... with the low-rank tap operator T_k Z (build_mic_lr)
     PATH_PIC_POLY = 1u << 16,      // perfect-CSI IC by polyphase synthesis / analysis (k_poly_*)
     PATH_WROW3 = 1u << 17,         // unfused W contraction as one GEMM per row tile (k_wrow3)
+    PATH_SNR_LOOP = 1u << 18,      // k_pic_fft ran in its SNR-loop form (Opts::snr_loop)
 };
 
 // Per-stage trace of one unit (dsce_trace_unit_ex): every kernel that forms one

@@ -1851,15 +1851,43 @@ __device__ __forceinline__ void dft6(double2 (&x)[6]) {
 // constellation; the constant rows of u (pilots) are per-lane LDS slots read
 // through the same address select, so a row's new u is one LDS read.
 // (vb / vn = the block's index in the grid and the grid's size, vb % 8 = the XCD)
-template <int NT, int SH, bool TRACE, bool S0>
+// LOOP (r07, with S0): the block owns 64 realisations x one symbol and walks
+// the chunk's SNR points k = 0 .. U / R - 1 itself (unit k R + rl).  What a
+// realisation's SNR points share runs once per block: the scalar prologue, the
+// tables and their barrier, xs / sidr / h / tap loads, the centring, 1 / h,
+// the constant-row slots, the masks and txp.  Per SNR point: the six y loads
+// (point k + 1's are issued as soon as point k's Yo is formed, so they fly
+// during its iterations: 24 VGPRs), Yo = c y / h + ofI, stage 0 and the
+// iterations, operation for operation what the per-unit form runs.  u needs no
+// reset between points: stage 0 takes nothing from it and its re-precode
+// rewrites all six rows (data rows from the decisions, the others from ucst).
+// The counts of every (point, stage) wait in LDS (cntl, PF_LOOP_CNT words per
+// wave: the launcher checks) for the one flush at the end, so the loop has no
+// barrier.  Grid: symbols x R / 64, symbol fastest inside each XCD's range
+// (k_txrx_fft's order).
+static constexpr int PF_LOOP_CNT = 128;     // (SNR points) x (stages) of one LOOP launch
+template <int NT, int SH, bool TRACE, bool S0, bool LOOP = false>
 __device__ __forceinline__ void pic_fft_body(const SchemeK& sk, const BandOrder& ord, const double2* __restrict__ ir, int N,
                                              const StorePerfectDetect& o, int niter, int vb, int vn) {
+    static_assert(!LOOP || S0, "the SNR loop carries stage 0 (u of the stage kernel is per unit)");
     int ug, blk;
-    band_block(ord, sk.QH.nblk, ug, blk, vb, vn);
+    if constexpr (LOOP) {
+        if (ord.xcd) {
+            const int L = xcd_remap(vb, vn);
+            blk = L % sk.QH.nblk;
+            ug = L / sk.QH.nblk;
+        } else {
+            ug = vb % ord.rgs;
+            blk = vb / ord.rgs;
+        }
+    } else {
+        band_block(ord, sk.QH.nblk, ug, blk, vb, vn);
+    }
     const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, r = l >> 4;
     const int U = o.U, R = o.R;
-    const int unit = ug * WAVE + w * 16 + (l & 15);
-    const int rl = unit % R;
+    const int nk = LOOP ? ord.nchunk : 1;                      // SNR points this block walks
+    const int unit0 = ug * WAVE + w * 16 + (l & 15);           // LOOP: the unit of point 0 = the realisation
+    const int rl = LOOP ? unit0 : unit0 % R;
     const int row0 = sk.QH.row0[blk], klo = sk.QH.klo[blk];
     const double cs = o.scI, rq = o.rQ;                        // the chain's scale (host: scI != 0), scQ / scI
     __shared__ double2 sym[256];
@@ -1868,16 +1896,18 @@ __device__ __forceinline__ void pic_fft_body(const SchemeK& sk, const BandOrder&
     __shared__ double2 rpv[24];
     __shared__ int rdc[24];
     __shared__ double2 amt[2][6][16];                          // A_m[i][k] at [dir][m][i + 4 k]
-    __shared__ int cntl[4][PM_MAXIT + 1];                      // [wave][stage]
+    __shared__ int cntl[4][LOOP ? PF_LOOP_CNT : PM_MAXIT + 1];  // [wave][stage]; LOOP: [wave][point (niter + 1) + stage]
     __shared__ double2 ucst[6][256];                            // the lane's constant rows of u (scaled)
     // decisions u (scaled) and the iteration-invariant Yo and 1 / h of the lane's
     // rows, and the channel taps of the lane's samples (registers for all iterations)
     double2 u[6], yh[6], hc[6];
+    double2 yr[LOOP ? 6 : 1];                                  // LOOP: raw y of the next SNR point, in flight
     unsigned txp[2] = {0u, 0u};
     double2 taps[6][NT];
     const __amdgpu_buffer_rsrc_t trs =
         buf_rsrc(ir + (size_t)klo * R, ((size_t)(NT - 1) * N + (N - klo)) * R * sizeof(double2));
     const unsigned tv0 = (unsigned)(6 * r * R + rl) * 16u;     // r is also the lane's time quarter
+    const RowView vy(o.y, row0, U, r, unit0, 16);
     {
         // table loads, then the per-unit loads (raw y and h into yh / hc), then
         // the LDS writes: the writes wait only for the tables (vmcnt retires in
@@ -1891,13 +1921,14 @@ __device__ __forceinline__ void pic_fft_body(const SchemeK& sk, const BandOrder&
         const double2 pv = sk.ct_rpv[blk * 24 + rt];
         const int rdv = sk.ct_rdc[blk * 24 + rt];
         const double2 nt = sk.ct_amt[min(tid, 191)];
-        const RowView vu = S0 ? RowView(o.xs, row0, R, r, rl, 16) : RowView(o.u, row0, U, r, unit, 16);
-        const RowView vs(o.sidr, row0, R, r, rl, 2), vy(o.y, row0, U, r, unit, 16), vh(o.h, row0, R, r, rl, 16);
+        const RowView vu = S0 ? RowView(o.xs, row0, R, r, rl, 16) : RowView(o.u, row0, U, r, unit0, 16);
+        const RowView vs(o.sidr, row0, R, r, rl, 2), vh(o.h, row0, R, r, rl, 16);
 #pragma unroll
         for (int b = 0; b < 6; ++b) {
             u[b] = vu.ld2(b);
             txp[b >> 2] |= (vs.ldu16(b) & 0xffu) << (8 * (b & 3));
-            yh[b] = vy.ld2(b);
+            if constexpr (LOOP) yr[b] = vy.ld2(b);
+            else yh[b] = vy.ld2(b);
             hc[b] = vh.ld2(b);
         }
 #pragma unroll
@@ -1966,128 +1997,159 @@ __device__ __forceinline__ void pic_fft_body(const SchemeK& sk, const BandOrder&
 #pragma unroll
         for (int a = 0; a < 6; ++a) u[a] = nv[a];
     };
-    if (S0) {
-        // stage 0: Yo = c y / h + (ofI, 0) and 1 / h now, one-tap, slicer,
-        // counts, decisions
-        int dp[6];
-        double fI[6], fQ[6];
+    if constexpr (LOOP) {
+        // 1 / h once for every SNR point
 #pragma unroll
         for (int a = 0; a < 6; ++a) {
-            const double2 hh = hc[a], yv = yh[a];
+            const double2 hh = hc[a];
             const double id = recip_fast(hh.x * hh.x + hh.y * hh.y);
             hc[a] = make_double2(hh.x * id, -hh.y * id);
-            const double2 ys = c_mulf(yv, hc[a]);
-            yh[a] = make_double2(fma(ys.x, cs, o.ofI), ys.y * cs);
-            fI[a] = yh[a].x;
-            fQ[a] = fma(yh[a].y, rq, o.ofQ);
         }
-        slice6(dp, fI, fQ, o.topI, o.topQ, sgrid);
-#pragma unroll
-        for (int a = 0; a < 6; ++a) {
-            const bool data = (dmask >> a) & 1;
-            ncnt += __umul24(__popc((unsigned)(dp[a] ^ (int)((txp[a >> 2] >> (8 * (a & 3))) & 0xffu))), cweight(a));
-            if (TRACE && data && trace_hit(o.tr, unit)) o.tr->dec_p[trace_ix(o.tr, (size_t)(rdc[4 * a + r] >> 1), unit)] = dp[a];
-        }
-        reprecode(dp);
-        cntl[w][0] = wave_sum_dpp(rl < o.rvalid ? ncnt : 0);
-        ncnt = 0;
     }
-    for (int it = 1; it <= niter; ++it) {
-        // an opaque zero keeps the per-iteration LDS matrix reads inside the loop
-        // (hoisted, they would hold 56 more registers)
-        int oz = 0;
-        asm volatile("" : "+v"(oz));
-        // t = IDFT24(u): DFT-6 per lane, then the 4-point network with the lane
-        // twiddle w24^(k m') (A_m, inverse): lane r ends with the time samples
-        // 6 r + m'
-        double2 x[6];
+    // the next point's y.  The last point reloads its own (in bounds, unused):
+    // under a uniform `k + 1 < nk` branch the compiler kept a second copy of yr
+    // across the join, 48 register copies per point, 256 VGPRs and 92 B of
+    // scratch in the trace instances, and the kernel measured 2 % slower.
+    // Issued behind stage 0's Yo; the trace instances, which have no registers
+    // to keep it in flight (24 more spilled), load it after the iterations
+    auto next_y = [&](int k) {
+        const unsigned ko = (unsigned)(min(k + 1, nk - 1) * R) * 16u;
 #pragma unroll
-        for (int a = 0; a < 6; ++a) x[a] = u[a];
-        dft6<1>(x);
-        double2 t[6];
-        const int ai = (l & 3) + 4 * (l >> 4) + oz;             // this lane's A entry
-#pragma unroll
-        for (int m = 0; m < 6; ++m) {
-            const double2 am = amt[0][m][ai], b = x[p6(m)];
-            t[m] = mfma4_cmul(am, b);
-        }
-        // channel, in place, last sample first: x[m] = sum_q IR_q[m] t[m - d_q];
-        // t[-1] of the quarter is sample 5 of the previous quarter's lane (the
-        // cyclic prefix for quarter 0)
-        const double2 tprev = bperm_c(((l + 48) & 63) * 4, t[5]);
-#pragma unroll
-        for (int m = 5; m >= 0; --m) {
-            const double2 tp = m ? t[m - 1] : tprev;
-            double2 acc = make_double2(0.0, 0.0);
-#pragma unroll
-            for (int q = 0; q < NT; ++q) c_fma(acc, taps[m][q], ((SH >> q) & 1) ? tp : t[m]);
-            t[m] = acc;
-        }
-        // acc = qs gs DFT24(x): the network back to lane r = output residue with
-        // the twiddle qs gs w24^-(i m') (A_m, forward), DFT-6
-#pragma unroll
-        for (int m = 0; m < 6; ++m) x[m] = mfma4_cmul(amt[1][m][ai], t[m]);
-        dft6<-1>(x);
-        // Yo and hcs at the first epilogue (not before the loop): the first chain
-        // runs while y and h are still in flight (S0: formed above)
-        if (it == 1 && !S0)
+        for (int a = 0; a < 6; ++a) yr[LOOP ? a : 0] = buf_ld2(vy.rs, vy.voff, (unsigned)a * vy.step + ko);
+    };
+    for (int k = 0; k < nk; ++k) {
+        const int unit = unit0 + k * R;                            // (!LOOP: one pass, unit0)
+        const int cb = LOOP ? k * (niter + 1) : 0;                 // the point's words of cntl
+        if (S0) {
+            // stage 0: Yo = c y / h + (ofI, 0) and 1 / h now, one-tap, slicer,
+            // counts, decisions
+            int dp[6];
+            double fI[6], fQ[6];
 #pragma unroll
             for (int a = 0; a < 6; ++a) {
-                const double2 hh = hc[a], yv = yh[a];
-                const double id = recip_fast(hh.x * hh.x + hh.y * hh.y);
-                hc[a] = make_double2(hh.x * id, -hh.y * id);        // 1 / h
+                const double2 yv = LOOP ? yr[a] : yh[a];
+                if constexpr (!LOOP) {
+                    const double2 hh = hc[a];
+                    const double id = recip_fast(hh.x * hh.x + hh.y * hh.y);
+                    hc[a] = make_double2(hh.x * id, -hh.y * id);
+                }
                 const double2 ys = c_mulf(yv, hc[a]);
-                yh[a] = make_double2(fma(ys.x, cs, o.ofI), ys.y * cs); // c y / h + (ofI, 0)
+                yh[a] = make_double2(fma(ys.x, cs, o.ofI), ys.y * cs);
+                fI[a] = yh[a].x;
+                fQ[a] = fma(yh[a].y, rq, o.ofQ);
             }
-        // epilogue per row 4a + r: the folded slicer input of z = y / h - acc / h
-        // (acc = c (D - diag h) u: centred taps), slicer, counts, re-precoded
-        // decision into u
-        int dp[6];
-        double fI[6], fQ[6];
+            if constexpr (LOOP && !TRACE) next_y(k);
+            slice6(dp, fI, fQ, o.topI, o.topQ, sgrid);
 #pragma unroll
-        for (int a = 0; a < 6; ++a) {
-            const double2 xa = x[p6(a)], hh = hc[a];
-            fI[a] = fma(-xa.x, hh.x, fma(xa.y, hh.y, yh[a].x));
-            fQ[a] = fma(fma(-xa.x, hh.y, fma(-xa.y, hh.x, yh[a].y)), rq, o.ofQ);
-            if (TRACE && ((dmask >> a) & 1) && o.tr->yperf && trace_hit(o.tr, unit)) {
-                const int row = row0 + 4 * a + r;
-                const double2 yv = o.y[(size_t)row * U + unit];
-                o.tr->yperf[trace_ix(o.tr, (size_t)it * o.tr->LK + row, unit)] = c_sub(yv, make_double2(xa.x / cs, xa.y / cs));
+            for (int a = 0; a < 6; ++a) {
+                const bool data = (dmask >> a) & 1;
+                ncnt += __umul24(__popc((unsigned)(dp[a] ^ (int)((txp[a >> 2] >> (8 * (a & 3))) & 0xffu))), cweight(a));
+                if (TRACE && data && trace_hit(o.tr, unit)) o.tr->dec_p[trace_ix(o.tr, (size_t)(rdc[4 * a + r] >> 1), unit)] = dp[a];
             }
+            reprecode(dp);
+            cntl[w][cb] = wave_sum_dpp(rl < o.rvalid ? ncnt : 0);
+            ncnt = 0;
         }
-        // a decision exactly on a mid-point (measure zero): the smallest symbol
-        // index among the tied grid points (one uniform branch inside)
-        slice6(dp, fI, fQ, o.topI, o.topQ, sgrid);
+        for (int it = 1; it <= niter; ++it) {
+            // an opaque zero keeps the per-iteration LDS matrix reads inside the loop
+            // (hoisted, they would hold 56 more registers)
+            int oz = 0;
+            asm volatile("" : "+v"(oz));
+            // t = IDFT24(u): DFT-6 per lane, then the 4-point network with the lane
+            // twiddle w24^(k m') (A_m, inverse): lane r ends with the time samples
+            // 6 r + m'
+            double2 x[6];
 #pragma unroll
-        for (int a = 0; a < 6; ++a) {
-            const bool data = (dmask >> a) & 1;
-            ncnt += __umul24(__popc((unsigned)(dp[a] ^ (int)((txp[a >> 2] >> (8 * (a & 3))) & 0xffu))), cweight(a));
-            if (TRACE && data && trace_hit(o.tr, unit))
-                o.tr->dec_p[trace_ix(o.tr, (size_t)it * o.tr->ND + (rdc[4 * a + r] >> 1), unit)] = dp[a];
+            for (int a = 0; a < 6; ++a) x[a] = u[a];
+            dft6<1>(x);
+            double2 t[6];
+            const int ai = (l & 3) + 4 * (l >> 4) + oz;             // this lane's A entry
+#pragma unroll
+            for (int m = 0; m < 6; ++m) {
+                const double2 am = amt[0][m][ai], b = x[p6(m)];
+                t[m] = mfma4_cmul(am, b);
+            }
+            // channel, in place, last sample first: x[m] = sum_q IR_q[m] t[m - d_q];
+            // t[-1] of the quarter is sample 5 of the previous quarter's lane (the
+            // cyclic prefix for quarter 0)
+            const double2 tprev = bperm_c(((l + 48) & 63) * 4, t[5]);
+#pragma unroll
+            for (int m = 5; m >= 0; --m) {
+                const double2 tp = m ? t[m - 1] : tprev;
+                double2 acc = make_double2(0.0, 0.0);
+#pragma unroll
+                for (int q = 0; q < NT; ++q) c_fma(acc, taps[m][q], ((SH >> q) & 1) ? tp : t[m]);
+                t[m] = acc;
+            }
+            // acc = qs gs DFT24(x): the network back to lane r = output residue with
+            // the twiddle qs gs w24^-(i m') (A_m, forward), DFT-6
+#pragma unroll
+            for (int m = 0; m < 6; ++m) x[m] = mfma4_cmul(amt[1][m][ai], t[m]);
+            dft6<-1>(x);
+            // Yo and hcs at the first epilogue (not before the loop): the first chain
+            // runs while y and h are still in flight (S0: formed above)
+            if (it == 1 && !S0)
+#pragma unroll
+                for (int a = 0; a < 6; ++a) {
+                    const double2 hh = hc[a], yv = yh[a];
+                    const double id = recip_fast(hh.x * hh.x + hh.y * hh.y);
+                    hc[a] = make_double2(hh.x * id, -hh.y * id);        // 1 / h
+                    const double2 ys = c_mulf(yv, hc[a]);
+                    yh[a] = make_double2(fma(ys.x, cs, o.ofI), ys.y * cs); // c y / h + (ofI, 0)
+                }
+            // epilogue per row 4a + r: the folded slicer input of z = y / h - acc / h
+            // (acc = c (D - diag h) u: centred taps), slicer, counts, re-precoded
+            // decision into u
+            int dp[6];
+            double fI[6], fQ[6];
+#pragma unroll
+            for (int a = 0; a < 6; ++a) {
+                const double2 xa = x[p6(a)], hh = hc[a];
+                fI[a] = fma(-xa.x, hh.x, fma(xa.y, hh.y, yh[a].x));
+                fQ[a] = fma(fma(-xa.x, hh.y, fma(-xa.y, hh.x, yh[a].y)), rq, o.ofQ);
+                if (TRACE && ((dmask >> a) & 1) && o.tr->yperf && trace_hit(o.tr, unit)) {
+                    const int row = row0 + 4 * a + r;
+                    const double2 yv = o.y[(size_t)row * U + unit];
+                    o.tr->yperf[trace_ix(o.tr, (size_t)it * o.tr->LK + row, unit)] = c_sub(yv, make_double2(xa.x / cs, xa.y / cs));
+                }
+            }
+            // a decision exactly on a mid-point (measure zero): the smallest symbol
+            // index among the tied grid points (one uniform branch inside)
+            slice6(dp, fI, fQ, o.topI, o.topQ, sgrid);
+#pragma unroll
+            for (int a = 0; a < 6; ++a) {
+                const bool data = (dmask >> a) & 1;
+                ncnt += __umul24(__popc((unsigned)(dp[a] ^ (int)((txp[a >> 2] >> (8 * (a & 3))) & 0xffu))), cweight(a));
+                if (TRACE && data && trace_hit(o.tr, unit))
+                    o.tr->dec_p[trace_ix(o.tr, (size_t)it * o.tr->ND + (rdc[4 * a + r] >> 1), unit)] = dp[a];
+            }
+            if (it < niter) reprecode(dp);                           // the last iteration's decisions are only counted
+            cntl[w][cb + it] = wave_sum_dpp(rl < o.rvalid ? ncnt : 0);    // uniform: every lane writes the same word
+            ncnt = 0;
         }
-        if (it < niter) reprecode(dp);                           // the last iteration's decisions are only counted
-        cntl[w][it] = wave_sum_dpp(rl < o.rvalid ? ncnt : 0);    // uniform: every lane writes the same word
-        ncnt = 0;
+        if constexpr (LOOP && TRACE) next_y(k);
     }
     // counters of every stage, summed over the block's 4 waves: thread
     // 2 (it - it0) + edge issues the block's one atomic per counter
+    // (LOOP: 2 (point (niter + 1) + it) + edge, nk (niter + 1) <= PF_LOOP_CNT)
     __syncthreads();
     constexpr int it0 = S0 ? 0 : 1;
-    if (tid < 2 * (niter + 1 - it0)) {
-        const int it = (tid >> 1) + it0, edge = tid & 1;
+    if (tid < 2 * (nk * (niter + 1) - it0)) {
+        const int ci = (tid >> 1) + it0, edge = tid & 1;
+        const int it = LOOP ? ci % (niter + 1) : ci;
         int v = 0;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) v += (cntl[k][it] >> (16 * edge)) & 0xffff;
-        const int snr = o.snr0 + (ug * WAVE) / R;
+        for (int k = 0; k < 4; ++k) v += (cntl[k][ci] >> (16 * edge)) & 0xffff;
+        const int snr = o.snr0 + (LOOP ? ci / (niter + 1) : (ug * WAVE) / R);
         const size_t i0 = o.cidx0 + (size_t)it + (size_t)snr * o.cstride_snr + (edge ? (size_t)o.cstride_edge : 0);
         if (v) atomicAdd(&o.counters[i0], (unsigned long long)v);
     }
 }
 
-template <int NT, int SH, bool TRACE, bool S0 = false>
+template <int NT, int SH, bool TRACE, bool S0 = false, bool LOOP = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_pic_fft(SchemeK sk, BandOrder ord, const double2* __restrict__ ir, int N, StorePerfectDetect o, int niter) {
-    pic_fft_body<NT, SH, TRACE, S0>(sk, ord, ir, N, o, niter, blockIdx.x, gridDim.x);
+    pic_fft_body<NT, SH, TRACE, S0, LOOP>(sk, ord, ir, N, o, niter, blockIdx.x, gridDim.x);
 }
 
 // ---------------------------------------------------------------------------
@@ -3187,28 +3249,48 @@ unsigned launch_mmse_stages(hipStream_t s, const SchemeK& sk, const MmseK& mm, c
     return PATH_MIC_FFT | PATH_MIC_STAGES | (use_lr ? PATH_MIC_LR : 0u);
 }
 
+// Opts::snr_loop's auto rule: a chain kernel takes its SNR-loop form when the
+// looped grid (`blocks` blocks, each nchunk times as long as a per-unit block)
+// still fills the device's resident slots (2 blocks of 256 threads per CU:
+// amdgpu_waves_per_eu(2, 2)) for SNR_LOOP_MIN_ROUNDS rounds; below that the tail
+// of the last round costs more than the hoisted prologue saves.  Measured at C2
+// (7 points, 14 symbols, 256 CUs): the loop loses 4 % at 1.75
+// rounds (batch 4096) and wins 6.5 % at 3.5 (8192), 10 % at 7, 13 % at 14 and
+// 15-17 % at 28 (65 536); the rule switches at 3, inside the measured win.
+static constexpr int SNR_LOOP_MIN_ROUNDS = 3;
+static bool snr_loop_fills(const Opts& op, long long blocks) {
+    if (op.dev_cus <= 0) throw std::logic_error("snr_loop: the context's CU count is not set (dsce_create)");
+    return blocks >= (long long)SNR_LOOP_MIN_ROUNDS * 2 * op.dev_cus;
+}
+
 unsigned launch_perfect_chain(hipStream_t s, const Opts& op, const SchemeK& sk, const ChannelK& ch, McBuffers& b,
                               const PerfectDetectArgs* pd, int niter, bool stage0) {
     if (!pic_fft_ok(op, sk, ch, b, niter))
         throw std::logic_error("launch_perfect_chain: no chain kernel for this scheme (perfect_chain_ok is false)");
     StorePerfectDetect o = chain_detect(sk, b, pd, 1);
     const BandOrder om{b.U / WAVE, b.U / b.R, b.R / WAVE, op.xcd};
-    const dim3 grid((b.U / WAVE) * sk.QH.nblk), blk(256);
+    // the SNR-loop form (Opts::snr_loop): a block per 64 realisations and symbol
+    const int nk = b.U / b.R;
+    const bool loop_ok = stage0 && (long long)nk * (niter + 1) <= PF_LOOP_CNT;
+    const bool loop = loop_ok && (op.snr_loop == 1 || (op.snr_loop < 0 && nk > 1 &&
+                                                       snr_loop_fills(op, (long long)(b.R / WAVE) * sk.QH.nblk)));
+    const dim3 grid((loop ? b.R / WAVE : b.U / WAVE) * sk.QH.nblk), blk(256);
     // stage0: the chain also runs stage 0 of the branch (with k_mic_pilot /
     // k_mic_data); otherwise stage 0 came from the stage kernel (u in HBM)
     if (!(o.scI != 0.0))
         throw std::logic_error("launch_perfect_chain: the chain's slicer scale is zero");
-#define LAUNCH_PF(NTV, SHV, S0V)                                                                               \
-    do {                                                                                                        \
-        if (b.tr)                                                                                               \
-            hipLaunchKernelGGL((k_pic_fft<NTV, SHV, true, S0V>), grid, blk, 0, s, sk, om, b.ir, ch.N, o, niter);  \
-        else                                                                                                    \
-            hipLaunchKernelGGL((k_pic_fft<NTV, SHV, false, S0V>), grid, blk, 0, s, sk, om, b.ir, ch.N, o, niter); \
+#define LAUNCH_PF(NTV, SHV, S0V, LPV)                                                                               \
+    do {                                                                                                             \
+        if (b.tr)                                                                                                    \
+            hipLaunchKernelGGL((k_pic_fft<NTV, SHV, true, S0V, LPV>), grid, blk, 0, s, sk, om, b.ir, ch.N, o, niter);  \
+        else                                                                                                         \
+            hipLaunchKernelGGL((k_pic_fft<NTV, SHV, false, S0V, LPV>), grid, blk, 0, s, sk, om, b.ir, ch.N, o, niter); \
     } while (0)
-#define LAUNCH_PF2(NTV, SHV)                        \
-    do {                                            \
-        if (stage0) LAUNCH_PF(NTV, SHV, true);      \
-        else LAUNCH_PF(NTV, SHV, false);            \
+#define LAUNCH_PF2(NTV, SHV)                               \
+    do {                                                   \
+        if (loop) LAUNCH_PF(NTV, SHV, true, true);         \
+        else if (stage0) LAUNCH_PF(NTV, SHV, true, false); \
+        else LAUNCH_PF(NTV, SHV, false, false);            \
     } while (0)
     const int sh = pic_fft_shift(ch);
     if (ch.ntap == 1) LAUNCH_PF2(1, 0);
@@ -3216,7 +3298,7 @@ unsigned launch_perfect_chain(hipStream_t s, const Opts& op, const SchemeK& sk, 
     else LAUNCH_PF2(2, 2);
 #undef LAUNCH_PF2
 #undef LAUNCH_PF
-    return PATH_PIC_FFT;
+    return PATH_PIC_FFT | (loop ? PATH_SNR_LOOP : 0u);
 }
 
 // ---------------------------------------------------------------------------

@@ -228,6 +228,8 @@ typedef struct {
                                                  (k_poly_syn / k_poly_chan / k_poly_ana, option pic_poly) */
 #define DSCE_PATH_WROW3           (1u << 17)  /* unfused W contraction of 32-row blocks as one GEMM per row tile,
                                                  B = hP v_c (k_wrow3) */
+#define DSCE_PATH_SNR_LOOP        (1u << 18)  /* k_pic_fft ran in its SNR-loop form: a block walks the SNR points
+                                                 of its 64 realisations (option snr_loop) */
 
 /* Jakes kernels (dsce_jakes_info out6[0]) */
 #define DSCE_JAKES_NONE      0   /* no realisation formed yet                                        */
@@ -478,7 +480,11 @@ int dsce_jakes_info(dsce_ctx* ctx, int32_t* out6);
  *   jakes_grp2 (1, the
  *   default: a channel with two non-zero taps forms the Jakes taps of the read
  *   windows with k_jakes_grp2 — both taps per wave, each Philox block drawn
- *   once; 0: k_jakes_grp, one tap per block; r06).
+ *   once; 0: k_jakes_grp, one tap per block; r06), snr_loop (k_pic_fft with its
+ *   stage 0: 1 = a block per 64 realisations and symbol walks the chunk's SNR
+ *   points, the per-realisation prologue once, DSCE_PATH_SNR_LOOP; 0 = a block
+ *   per 64 units; -1, the default: the loop where its grid still fills the
+ *   device; same counts either way).
  * Retired after r06 (no scheme or channel selected their other values;
  * DSCE_EINVAL): pic_net, mic_net (the DPP form of the chain kernels' 4-point
  * network; the matrix-core form is the only one), stage_rb (k_stage_fused runs 8

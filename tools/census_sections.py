@@ -4,7 +4,8 @@
   tools/isa.sh builds the device assembly (/tmp/isa/kmc.s); then
   python3 tools/census_sections.py /tmp/isa/kmc.s k_pic_fftILi2ELi2ELb0ELb1EE [more.s PATTERN ...]
 
-The loop is every block LLVM annotates "in Loop" (plus its header).  Each
+The loop is every block LLVM annotates "in Loop" (plus its header); in a kernel
+with nested loops (the SNR-loop forms) it is the innermost depth.  Each
 instruction is attributed to a section by its opcode family:
   network     v_mfma (the 4-point network / ones-MFMA sums) and ds_bpermute
   fp64        v_{fma,fmac,add,mul}_f64 (DFT-6 pairs, taps, the one-tap epilogue)
@@ -49,6 +50,12 @@ def section(op, line):
     return "scalar"
 
 
+def block_depth(t):
+    """Loop depth a block label's annotation states (0: none); "Child Loop" lines name other blocks"""
+    m = re.search(r"(?:in Loop: Header=\S+|Loop Header:) Depth=(\d+)", t)
+    return int(m.group(1)) if m else 0
+
+
 def census(path, pat):
     lines = open(path).read().split("\n")
     start = None
@@ -63,23 +70,28 @@ def census(path, pat):
     while not lines[end].strip().startswith(".Lfunc_end"):
         end += 1
     body = lines[start:end]
-    whole, loop = Counter(), Counter()
-    in_loop = False
+    whole, depths = Counter(), {}
+    depth, label = 0, False
     for ln in body:
         t = ln.strip()
         if not t:
             continue
         if t.startswith(".LBB") or t.startswith("; %bb."):
-            in_loop = "in Loop" in t or "Loop Header" in t
+            depth, label = block_depth(t), True
             continue
+        if label and t.startswith(";"):
+            # the annotation of a nested loop's header continues on comment lines
+            depth = max(depth, block_depth(t))
+            continue
+        label = False
         if t.startswith((";", ".")):
             continue
         op = t.split()[0]
         sec = section(op, t)
         whole[sec] += 1
-        if in_loop:
-            loop[sec] += 1
-    return whole, loop
+        if depth:
+            depths.setdefault(depth, Counter())[sec] += 1
+    return whole, depths[max(depths)] if depths else Counter()
 
 
 def main():
