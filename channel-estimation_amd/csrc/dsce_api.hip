@@ -153,6 +153,9 @@ struct Scheme {
     // build_poly: largest |G - A w C| / max|G| or the same of Q (-1: not evaluated)
     double poly_resid = -1.0;
     double poly_nnz_a = 0.0, poly_nnz_b = 0.0;   // non-zero window samples of G's / Q's symbols
+    // soft demapper (dsce_llr_awgn, dsce_export_llr): its tables, and ||Q[:, l]||^2 per row l (device)
+    LlrTab llr{};
+    double* qn = nullptr;
 };
 
 }  // namespace dsce
@@ -494,6 +497,58 @@ void build_chain_tables(dsce_ctx* c, Scheme& s, const std::vector<int>& grid, co
     k.ct_wrow = dupload(c, wrow);
 }
 
+// Soft demapper tables of a scheme (LlrTab): for each bit of the label whether it
+// depends on one axis of the slicer grid only, and on which levels of it the bit
+// is 1.  The per-axis form is kept only if every bit is axis-pure and both axes
+// have at most 16 levels; the full-table form serves every other labelling.
+// Also ||Q[:, l]||^2, the factor between pn_time and the AWGN power of y_l.
+void build_llr_tables(dsce_ctx* c, Scheme& s, const std::vector<double>& lvI, const std::vector<double>& lvQ,
+                      const std::vector<int>& grid) {
+    LlrTab& t = s.llr;
+    t = LlrTab{};
+    t.symbols = s.k.symbols;
+    t.M = s.d.mod_order;
+    t.m = s.d.bits_per_symbol;
+    const int nI = (int)lvI.size(), nQ = (int)lvQ.size();
+    bool pure = nI <= 16 && nQ <= 16 && t.m <= 8;
+    for (int b = 0; b < t.m && pure; ++b) {
+        auto bit = [&](int iI, int iQ) { return (grid[(size_t)iI * nQ + iQ] >> b) & 1; };
+        bool onI = true, onQ = true;               // the bit is a function of iI / of iQ alone
+        for (int iI = 0; iI < nI; ++iI)
+            for (int iQ = 0; iQ < nQ; ++iQ) {
+                onI = onI && bit(iI, iQ) == bit(iI, 0);
+                onQ = onQ && bit(iI, iQ) == bit(0, iQ);
+            }
+        if (!onI && !onQ) {
+            pure = false;
+            break;
+        }
+        const int ax = onI ? 0 : 1;
+        unsigned mask = 0;
+        for (int i = 0; i < (ax ? nQ : nI); ++i) mask |= (unsigned)(ax ? bit(0, i) : bit(i, 0)) << i;
+        t.axis[b] = (unsigned char)ax;
+        t.mask[b] = (unsigned short)mask;
+        ++t.nbit[ax];
+    }
+    t.per_axis = pure ? 1 : 0;
+    if (pure) {
+        t.nI = nI;
+        t.nQ = nQ;
+        for (int i = 0; i < nI; ++i) t.lvI[i] = lvI[i];
+        for (int i = 0; i < nQ; ++i) t.lvQ[i] = lvQ[i];
+    }
+    std::vector<double> qn(s.LK, 0.0);
+    for (int l = 0; l < s.LK; ++l) {
+        double acc = 0.0;
+        for (int n = 0; n < s.N; ++n) {
+            const double2 q = s.Q[(size_t)l * s.N + n];
+            acc += q.x * q.x + q.y * q.y;
+        }
+        qn[l] = acc;
+    }
+    s.qn = dupload(c, qn);
+}
+
 // ---------------------------------------------------------------------------
 // operator packing
 // ---------------------------------------------------------------------------
@@ -770,6 +825,7 @@ void pack_scheme(dsce_ctx* c, Scheme& s) {
         }
         if (s.k.pf_ok) build_chain_tables(c, s, grid, row_data, row_cons, row_pcol, row_pval);
     }
+    build_llr_tables(c, s, lvI, lvQ, grid);
     // bits per realisation
     s.bits_all = (int64_t)s.d.n_data * s.d.bits_per_symbol;
     int64_t ce = 0;
@@ -2589,51 +2645,64 @@ int dsce_export(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, ui
     API_END
 }
 
-// Bulk per-stage export (ABI 10): run_batch for one scheme with the stage kernels
-// in TraceK's bulk mode (struct Bulk), k_export_stages after each SNR chunk.
-// Scratch counters, no MSE sums, Scheme::path restored.  A batch is cut into
-// sub-batches of whole waves so that the bulk arrays stay within option
-// export_stage_mb (every realisation is its own Philox streams: the cut does not
-// show).  On a multi-device handle the handle itself is member 0.
-int dsce_export_stages(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, uint64_t n_rep, uint32_t flags,
-                       const dsce_export_stages_out* out) {
-    TraceRange trace_range("dsce export stages");
-    API_BEGIN
-    check_ctx(ctx);
+// The bulk exports behind run_batch (dsce_export_stages, dsce_export_llr): the
+// entry checks they share, and the loop over sub-batches.
+extern "C++" {
+namespace {
+struct BulkFields {
+    const char* what;           // the entry point's name, for messages
+    int n;                      // fields (<= 5)
+    void* dst[5];               // caller's destinations (null: not requested)
+    size_t per_rep[5];          // elements per realisation
+    size_t esz[5];              // bytes per element
+};
+
+Scheme& bulk_export_check(dsce_ctx* ctx, int32_t id, const void* out, uint32_t flags, uint32_t allowed,
+                          const char* what) {
+    const std::string w(what);
     if (!ctx->chan_set) throw ApiError(DSCE_ESTATE, "dsce_set_channel first");
     if (ctx->nsnr <= 0) throw ApiError(DSCE_ESTATE, "dsce_set_snr first");
     if (ctx->schemes.empty()) throw ApiError(DSCE_ESTATE, "no scheme added");
     Scheme& s = get_scheme(ctx, id);
-    if (!out) throw ApiError(DSCE_EINVAL, "dsce_export_stages: null out");
-    if (flags & ~(uint32_t)(DSCE_EXPORT_F32 | DSCE_EXPORT_DEVICE))
-        throw ApiError(DSCE_EINVAL, "dsce_export_stages: unknown flag");
-    // fields in k_export_stages' order
-    void* dst[5] = {out->hp_ls, out->h_est, out->y_ic, out->dec_est, out->dec_perf};
+    if (!out) throw ApiError(DSCE_EINVAL, w + ": null out");
+    if (flags & ~allowed) throw ApiError(DSCE_EINVAL, w + ": unknown flag");
+    return s;
+}
+
+void bulk_fields_check(dsce_ctx* ctx, const Scheme& s, const BulkFields& f, bool to_device) {
+    const std::string w(f.what);
     bool any = false;
-    for (void* p : dst) any = any || p;
-    if (!any) throw ApiError(DSCE_EINVAL, "dsce_export_stages: no field requested");
+    for (int i = 0; i < f.n; ++i) any = any || f.dst[i];
+    if (!any) throw ApiError(DSCE_EINVAL, w + ": no field requested");
     if (!(s.mmse_ready && s.Wd))
-        throw ApiError(DSCE_ESTATE, "dsce_export_stages: dsce_build_mmse first (or dsce_set_interpolation with n_iter 0)");
+        throw ApiError(DSCE_ESTATE, w + ": dsce_build_mmse first (or dsce_set_interpolation with n_iter 0)");
     if (s.interp && ctx->niter > 0)
-        throw ApiError(DSCE_ESTATE, "dsce_export_stages: interference-cancellation iterations need the MMSE estimator "
-                                    "(n_iter must be 0 with an interpolation estimator)");
-    const bool f32 = (flags & DSCE_EXPORT_F32) != 0, to_device = (flags & DSCE_EXPORT_DEVICE) != 0;
+        throw ApiError(DSCE_ESTATE, w + ": interference-cancellation iterations need the MMSE estimator "
+                                        "(n_iter must be 0 with an interpolation estimator)");
     if (to_device)
-        for (void* p : dst) {
-            if (!p) continue;
+        for (int i = 0; i < f.n; ++i) {
+            if (!f.dst[i]) continue;
             hipPointerAttribute_t at{};
-            const hipError_t e = hipPointerGetAttributes(&at, p);
+            const hipError_t e = hipPointerGetAttributes(&at, f.dst[i]);
             if (e != hipSuccess) (void)hipGetLastError();
             if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != ctx->device)
-                throw ApiError(DSCE_EINVAL, "dsce_export_stages: DSCE_EXPORT_DEVICE with a pointer that is not device "
-                                            "memory of the context's GPU");
+                throw ApiError(DSCE_EINVAL, w + ": DSCE_EXPORT_DEVICE with a pointer that is not device "
+                                                "memory of the context's GPU");
         }
+}
+
+// run_batch for scheme `id` with the stage kernels in TraceK's bulk mode (struct
+// Bulk), `launch` after each SNR chunk.  Scratch counters, no MSE sums,
+// Scheme::path restored.  A batch is cut into sub-batches of whole waves so that
+// the bulk arrays stay within option export_stage_mb (every realisation is its
+// own Philox streams: the cut does not show).  launch(bk, out, row0, R, nvalid,
+// snr0): the export kernel of the chunk that starts at SNR index snr0, from the
+// bulk arrays of bk into out[] (the caller's device memory, realisation 0 of the
+// sub-batch at row row0; or the staging buffer, at row 0).
+template <class Launch>
+void bulk_export(dsce_ctx* ctx, Scheme& s, int32_t id, uint64_t seed, uint64_t first_rep, uint64_t n_rep,
+                 bool to_device, const BulkFields& f, Launch launch) {
     const int LK = s.LK, NP = s.d.n_pilots, ND = s.d.n_data, nsnr = ctx->nsnr, S = ctx->niter + 1;
-    const size_t csz = f32 ? sizeof(float2) : sizeof(double2);
-    const int flen[5] = {NP, LK, LK, ND, ND};
-    const size_t esz[5] = {csz, csz, csz, sizeof(int32_t), sizeof(int32_t)};
-    size_t per_rep[5];
-    for (int f = 0; f < 5; ++f) per_rep[f] = (size_t)nsnr * S * flen[f];
     // the bulk trace arrays of one unit: hP, diag(D_hat), y_ic and both decisions of every stage
     const int chunk = snr_chunk(ctx);
     const size_t unit_bytes = (size_t)S * (((size_t)NP + 2 * (size_t)LK) * sizeof(double2) + 2 * (size_t)ND * sizeof(int));
@@ -2671,16 +2740,16 @@ int dsce_export_stages(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_
             const int nvalid = (int)std::min<uint64_t>((uint64_t)R, left);
             ensure_buffers(ctx, ctx->batch);
             ctx->buf.mse_err = ctx->buf.mse_pow = nullptr;
-            ExportStagesK ek{};
-            ek.row0 = to_device ? (long long)done : 0;
+            void* out[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+            const long long row0 = to_device ? (long long)done : 0;
             if (to_device) {
-                for (int f = 0; f < 5; ++f) ek.out[f] = dst[f];
+                for (int i = 0; i < f.n; ++i) out[i] = f.dst[i];
             } else {
                 // one sub-batch of every requested field, each 256-byte aligned
                 size_t off[5], total = 0;
-                for (int f = 0; f < 5; ++f) {
-                    off[f] = total;
-                    if (dst[f]) total += ((size_t)nvalid * per_rep[f] * esz[f] + 255) / 256 * 256;
+                for (int i = 0; i < f.n; ++i) {
+                    off[i] = total;
+                    if (f.dst[i]) total += ((size_t)nvalid * f.per_rep[i] * f.esz[i] + 255) / 256 * 256;
                 }
                 if (total > ctx->exp_stage_bytes) {
                     if (ctx->exp_stage) {
@@ -2692,33 +2761,15 @@ int dsce_export_stages(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_
                     DSCE_HIP_CHECK(hipMalloc(&ctx->exp_stage, total));
                     ctx->exp_stage_bytes = total;
                 }
-                for (int f = 0; f < 5; ++f) ek.out[f] = dst[f] ? (char*)ctx->exp_stage + off[f] : nullptr;
+                for (int i = 0; i < f.n; ++i) out[i] = f.dst[i] ? (char*)ctx->exp_stage + off[i] : nullptr;
             }
-            ek.src[0] = bk.hp;
-            ek.src[1] = bk.k.hest;
-            ek.src[2] = bk.k.yest;
-            ek.src[3] = bk.k.dec_e;
-            ek.src[4] = bk.k.dec_p;
-            for (int f = 0; f < 5; ++f) {
-                ek.len[f] = flen[f];
-                ek.tiles[f] = dst[f] ? (flen[f] + EXPORT_TILE - 1) / EXPORT_TILE : 0;
-            }
-            ek.S = S;
-            ek.R = R;
-            ek.nsnr = nsnr;
-            ek.rvalid = nvalid;
-            bk.flush = [&](int snr0) {
-                ek.U = ctx->buf.U;
-                ek.snr0 = snr0;
-                Timed t(ctx, "k_export_stages");
-                launch_export_stages(ctx->stream, ek, f32);
-            };
+            bk.flush = [&](int snr0) { launch(bk, out, row0, R, nvalid, snr0); };
             run_batch(ctx, seed, first_rep + done, R, nvalid, nullptr, &bk);
             if (!to_device)
-                for (int f = 0; f < 5; ++f)
-                    if (dst[f])
-                        DSCE_HIP_CHECK(hipMemcpyAsync((char*)dst[f] + (size_t)done * per_rep[f] * esz[f], ek.out[f],
-                                                      (size_t)nvalid * per_rep[f] * esz[f], hipMemcpyDeviceToHost,
+                for (int i = 0; i < f.n; ++i)
+                    if (f.dst[i])
+                        DSCE_HIP_CHECK(hipMemcpyAsync((char*)f.dst[i] + (size_t)done * f.per_rep[i] * f.esz[i], out[i],
+                                                      (size_t)nvalid * f.per_rep[i] * f.esz[i], hipMemcpyDeviceToHost,
                                                       ctx->stream));
             done += (uint64_t)nvalid;
         }
@@ -2730,6 +2781,149 @@ int dsce_export_stages(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_
         throw;
     }
     for (void* p : tmp) DSCE_HIP_CHECK(hipFree(p));
+}
+
+}  // namespace
+}  // extern "C++"
+
+// Bulk per-stage export (ABI 10): bulk_export with k_export_stages after each SNR
+// chunk.  On a multi-device handle the handle itself is member 0.
+int dsce_export_stages(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, uint64_t n_rep, uint32_t flags,
+                       const dsce_export_stages_out* out) {
+    TraceRange trace_range("dsce export stages");
+    API_BEGIN
+    check_ctx(ctx);
+    Scheme& s = bulk_export_check(ctx, id, out, flags, DSCE_EXPORT_F32 | DSCE_EXPORT_DEVICE, "dsce_export_stages");
+    const bool f32 = (flags & DSCE_EXPORT_F32) != 0, to_device = (flags & DSCE_EXPORT_DEVICE) != 0;
+    const int LK = s.LK, NP = s.d.n_pilots, ND = s.d.n_data, nsnr = ctx->nsnr, S = ctx->niter + 1;
+    const size_t csz = f32 ? sizeof(float2) : sizeof(double2);
+    // fields in k_export_stages' order
+    const int flen[5] = {NP, LK, LK, ND, ND};
+    BulkFields f{"dsce_export_stages", 5, {out->hp_ls, out->h_est, out->y_ic, out->dec_est, out->dec_perf}, {},
+                 {csz, csz, csz, sizeof(int32_t), sizeof(int32_t)}};
+    for (int i = 0; i < 5; ++i) f.per_rep[i] = (size_t)nsnr * S * flen[i];
+    bulk_fields_check(ctx, s, f, to_device);
+    bulk_export(ctx, s, id, seed, first_rep, n_rep, to_device, f,
+                [&](const Bulk& bk, void* const* dst, long long row0, int R, int nvalid, int snr0) {
+                    ExportStagesK ek{};
+                    ek.src[0] = bk.hp;
+                    ek.src[1] = bk.k.hest;
+                    ek.src[2] = bk.k.yest;
+                    ek.src[3] = bk.k.dec_e;
+                    ek.src[4] = bk.k.dec_p;
+                    for (int i = 0; i < 5; ++i) {
+                        ek.len[i] = flen[i];
+                        ek.tiles[i] = dst[i] ? (flen[i] + EXPORT_TILE - 1) / EXPORT_TILE : 0;
+                        ek.out[i] = dst[i];
+                    }
+                    ek.S = S;
+                    ek.R = R;
+                    ek.nsnr = nsnr;
+                    ek.rvalid = nvalid;
+                    ek.row0 = row0;
+                    ek.U = ctx->buf.U;
+                    ek.snr0 = snr0;
+                    Timed t(ctx, "k_export_stages");
+                    launch_export_stages(ctx->stream, ek, f32);
+                });
+    API_END
+}
+
+// Bulk soft outputs (DSCE_HAS_LLR): bulk_export with k_llr after each SNR chunk:
+// x_est, pn_eff and the LLRs of every stage of the MMSE branch from the bulk
+// arrays y_ic / h_est.  On a multi-device handle the handle itself is member 0.
+int dsce_export_llr(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, uint64_t n_rep, uint32_t flags,
+                    const dsce_export_llr_out* out) {
+    TraceRange trace_range("dsce export llr");
+    API_BEGIN
+    check_ctx(ctx);
+    Scheme& s = bulk_export_check(ctx, id, out, flags, DSCE_EXPORT_F32 | DSCE_EXPORT_DEVICE | DSCE_LLR_MAXLOG,
+                                  "dsce_export_llr");
+    const bool f32 = (flags & DSCE_EXPORT_F32) != 0, to_device = (flags & DSCE_EXPORT_DEVICE) != 0;
+    const int ND = s.d.n_data, nsnr = ctx->nsnr, S = ctx->niter + 1, m = s.d.bits_per_symbol;
+    const size_t rsz = f32 ? sizeof(float) : sizeof(double);
+    const size_t per = (size_t)nsnr * S * ND;
+    // fields in k_llr's order
+    BulkFields f{"dsce_export_llr", 3, {out->x_est, out->pn_eff, out->llr}, {per, per, per * m}, {2 * rsz, rsz, rsz}};
+    bulk_fields_check(ctx, s, f, to_device);
+    bulk_export(ctx, s, id, seed, first_rep, n_rep, to_device, f,
+                [&](const Bulk& bk, void* const* dst, long long row0, int R, int nvalid, int snr0) {
+                    LlrK a{};
+                    a.tab = s.llr;
+                    a.yic = bk.k.yest;
+                    a.hest = bk.k.hest;
+                    a.pn = ctx->d_pn;
+                    a.qn = s.qn;
+                    a.data_pos = s.k.data_pos;
+                    a.ph_ptr = s.k.ph_ptr;
+                    a.ph_col = s.k.ph_col;
+                    a.ph_val = s.k.ph_val;
+                    a.data_div = s.k.data_div;
+                    a.despread = s.k.despread;
+                    a.real_detect = s.k.real_detect;
+                    a.maxlog = (flags & DSCE_LLR_MAXLOG) ? 1 : 0;
+                    a.NP = s.k.NP;
+                    a.LK = s.LK;
+                    a.ND = ND;
+                    a.S = S;
+                    a.R = R;
+                    a.U = ctx->buf.U;
+                    a.snr0 = snr0;
+                    a.nsnr = nsnr;
+                    a.rvalid = nvalid;
+                    a.row0 = row0;
+                    for (int i = 0; i < 3; ++i) a.out[i] = dst[i];
+                    Timed t(ctx, "k_llr");
+                    launch_llr(ctx->stream, a, f32);
+                });
+    API_END
+}
+
+int dsce_llr_awgn(dsce_ctx* ctx, int32_t id, uint32_t flags, const double* x, const double* pn, int64_t n_pn,
+                  int64_t n, double* llr_out) {
+    API_BEGIN
+    check_ctx(ctx);
+    Scheme& s = get_scheme(ctx, id);
+    if (flags & ~(uint32_t)DSCE_LLR_MAXLOG) throw ApiError(DSCE_EINVAL, "dsce_llr_awgn: unknown flag");
+    if (n < 0) throw ApiError(DSCE_EINVAL, "dsce_llr_awgn: n < 0");
+    if (n_pn != 1 && n_pn != n) throw ApiError(DSCE_EINVAL, "dsce_llr_awgn: n_pn must be 1 or n");
+    if (n > 0 && (!x || !pn || !llr_out)) throw ApiError(DSCE_EINVAL, "dsce_llr_awgn: null pointer");
+    if (n > 0) {
+        const int m = s.d.bits_per_symbol;
+        std::vector<void*> tmp;
+        auto talloc = [&](size_t bytes) {
+            void* p;
+            DSCE_HIP_CHECK(hipMalloc(&p, bytes));
+            tmp.push_back(p);
+            return p;
+        };
+        try {
+            double2* dx = (double2*)talloc((size_t)n * sizeof(double2));
+            double* dp = (double*)talloc((size_t)n_pn * sizeof(double));
+            double* dl = (double*)talloc((size_t)n * m * sizeof(double));
+            DSCE_HIP_CHECK(hipMemcpyAsync(dx, x, (size_t)n * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
+            DSCE_HIP_CHECK(hipMemcpyAsync(dp, pn, (size_t)n_pn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+            launch_llr_probe(ctx->stream, s.llr, dx, dp, n_pn, n, (flags & DSCE_LLR_MAXLOG) != 0, dl);
+            DSCE_HIP_CHECK(hipGetLastError());
+            DSCE_HIP_CHECK(hipMemcpyAsync(llr_out, dl, (size_t)n * m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+            DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        } catch (...) {
+            (void)hipStreamSynchronize(ctx->stream);
+            for (void* p : tmp) (void)hipFree(p);
+            throw;
+        }
+        for (void* p : tmp) DSCE_HIP_CHECK(hipFree(p));
+    }
+    API_END
+}
+
+int dsce_llr_info(dsce_ctx* ctx, int32_t id, int32_t* out2) {
+    API_BEGIN
+    check_ctx(ctx);
+    Scheme& s = get_scheme(ctx, id);
+    if (!out2) throw ApiError(DSCE_EINVAL, "null output");
+    out2[0] = s.llr.per_axis;
+    out2[1] = s.llr.m;
     API_END
 }
 

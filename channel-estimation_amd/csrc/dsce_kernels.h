@@ -307,6 +307,47 @@ struct ExportStagesK {
 };
 void launch_export_stages(hipStream_t s, const ExportStagesK& a, bool f32);
 
+// Soft demapper of a scheme's constellation (kernels_llr.hip; dsce_llr_awgn,
+// dsce_export_llr), derived at dsce_add_scheme.  per_axis: every bit of the label
+// depends on one axis of the slicer grid only, so its LLR is a PAM LLR over that
+// axis' levels (axis[b]: 0 = I, 1 = Q; mask[b]: the levels where bit b is 1);
+// else the full-table form over `symbols` (bit b of symbol i is (i >> b) & 1).
+// Passed by value: the tables are kernel arguments (uniform loads).
+struct LlrTab {
+    const double2* symbols;   // M, sorted by bit label (device)
+    int M, m, per_axis;
+    int nI, nQ;               // per_axis: levels per axis (<= 16)
+    int nbit[2];              // per_axis: bits on each axis
+    double lvI[16], lvQ[16];  // ascending, 0 past nI / nQ
+    unsigned short mask[8];
+    unsigned char axis[8];
+};
+// Bulk per-stage soft outputs of one batch and SNR chunk after its last stage
+// (k_llr; dsce_export_llr): from the bulk trace arrays y_ic / h_est
+// [stage][LK][U] the demapper input x_est, its noise power pn_eff and the m LLRs
+// of every data symbol, written [rep][snr][stage][ND]( [m]) like k_export_stages.
+// Fields in the order x_est (complex), pn_eff, llr (real).
+struct LlrK {
+    LlrTab tab;
+    const double2* yic;       // [S][LK][U]
+    const double2* hest;      // [S][LK][U]
+    const double* pn;         // [nsnr] AWGN power per time sample
+    const double* qn;         // [LK] ||Q[:, l]||^2
+    const int* data_pos;      // select mode: ND rows
+    const int* ph_ptr;        // despread: P^H in CSR (SchemeK::ph_*)
+    const int* ph_col;
+    const double2* ph_val;
+    double data_div;
+    int despread, real_detect, maxlog;
+    int NP, LK, ND, S, R, U, snr0, nsnr, rvalid;
+    long long row0;
+    void* out[3];             // null: not requested
+};
+void launch_llr(hipStream_t s, const LlrK& a, bool f32);
+// LLRs of n points x (pn: one value or one per point), out [n][m]
+void launch_llr_probe(hipStream_t s, const LlrTab& t, const double2* x, const double* pn, long long n_pn, long long n,
+                      bool maxlog, double* out);
+
 // setup (correlation matrices and MMSE estimator)
 struct SetupArgs {
     int N, LK, NP, Nsym, ntap, nsnr;

@@ -22,7 +22,13 @@ s = 0 (one-tap) .. n_iter (dsce_export_stages; --n-iter, default 4 as in the
 script): hp_ls_stages [n][n_snr][S][NP], h_est_stages and y_ic_stages
 [n][n_snr][S][LK], the detected symbol indices dec_est / dec_perf
 [n][n_snr][S][ND] int32 of the MMSE and the perfect-CSI branch, and n_iter in
-the metadata.  bit_errors(sym, dec) counts their bit errors per (SNR, stage)."""
+the metadata.  bit_errors(sym, dec) counts their bit errors per (SNR, stage).
+
+--llr exact|maxlog adds the soft outputs of the MMSE branch per stage
+(dsce_export_llr; the stage settings of --stages, --n-iter): the demapper input
+x_est [n][n_snr][S][ND], its noise power pn_eff (same shape, float32 / float64)
+and llr [n][n_snr][S][ND][m], positive = bit 1, and llr_method and n_iter in the
+metadata."""
 from __future__ import annotations
 
 import argparse
@@ -38,6 +44,8 @@ FIELDS = ("y", "hp_ls", "h_est", "h", "xp", "sym")
 STAGE_NAMES = {"hp_ls": "hp_ls_stages", "h_est": "h_est_stages", "y_ic": "y_ic_stages", "dec_est": "dec_est",
                "dec_perf": "dec_perf"}
 STAGE_ARRAYS = tuple(STAGE_NAMES.values())
+# dsce_export_llr fields (--llr), under their own names; the method is metadata key "llr_method"
+LLR_ARRAYS = ("x_est", "pn_eff", "llr")
 
 
 def bit_errors(sym, dec, considered=None):
@@ -79,7 +87,7 @@ def write_shard(path, arrays, meta):
     file, then os.replace).  meta must carry first_rep and n_rep."""
     n = int(meta["n_rep"])
     for k, a in arrays.items():
-        if k not in FIELDS and k not in STAGE_ARRAYS:
+        if k not in FIELDS and k not in STAGE_ARRAYS and k not in LLR_ARRAYS:
             raise ValueError("unknown field %r" % k)
         if a.shape[0] != n:
             raise ValueError("field %s holds %d realisations, the shard %d" % (k, a.shape[0], n))
@@ -140,7 +148,9 @@ def parser():
     ap.add_argument("--no-mmse", action="store_true", help="skip dsce_build_mmse and the h_est field")
     ap.add_argument("--stages", action="store_true",
                     help="add the per-stage IC arrays (hp_ls_stages, h_est_stages, y_ic_stages, dec_est, dec_perf)")
-    ap.add_argument("--n-iter", type=int, default=None, help="IC iterations of --stages (default 4)")
+    ap.add_argument("--llr", choices=("exact", "maxlog"), default=None,
+                    help="add the soft outputs of the MMSE branch per stage (x_est, pn_eff, llr)")
+    ap.add_argument("--n-iter", type=int, default=None, help="IC iterations of --stages / --llr (default 4)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", required=True, help="shard prefix: writes PREFIX-00000.npz ...")
     return ap
@@ -150,17 +160,18 @@ def main(argv=None):
     a = parser().parse_args(argv)
     if a.reps < 1 or a.shard_reps < 1 or a.first_rep < 0:
         raise SystemExit("--reps and --shard-reps must be >= 1, --first-rep >= 0")
-    if a.n_iter is not None and not a.stages:
-        raise SystemExit("--n-iter belongs to --stages")
-    if a.stages and a.no_mmse:
-        raise SystemExit("--stages needs the MMSE estimator (drop --no-mmse)")
+    staged = a.stages or a.llr is not None
+    if a.n_iter is not None and not staged:
+        raise SystemExit("--n-iter belongs to --stages / --llr")
+    if staged and a.no_mmse:
+        raise SystemExit("--stages / --llr need the MMSE estimator (drop --no-mmse)")
     if a.n_iter is not None and a.n_iter < 0:
         raise SystemExit("--n-iter must be >= 0")
 
     from dsce.configs import build_setup
     from dsce.engine import ABI_VERSION, build_engine, gpu_tx
 
-    kw = dict(n_iter=4 if a.n_iter is None else a.n_iter) if a.stages else {}
+    kw = dict(n_iter=4 if a.n_iter is None else a.n_iter) if staged else {}
     S = build_setup(a.config, schemes=(a.scheme,), snr_db=a.snr_db, tx=gpu_tx(a.device), **kw)
     sc = S.schemes[a.scheme]
     eng = build_engine(S, device=a.device, batch=max(64, min(a.batch, a.reps)), mmse=not a.no_mmse)
@@ -170,14 +181,18 @@ def main(argv=None):
                 pilot_pos=np.asarray(sc.pilot_pos, dtype=np.int32), data_pos=np.asarray(sc.data_pos, dtype=np.int32),
                 symbols=np.asarray(sc.const.SymbolMapping, dtype=np.complex128).ravel(), kappa=float(sc.kappa),
                 data_div=float(sc.data_div), L=int(S.L), K=int(sc.LK // S.L), abi=int(ABI_VERSION))
-    if a.stages:
+    if staged:
         base["n_iter"] = int(S.n_iter)
+    if a.llr is not None:
+        base["llr_method"] = a.llr
     try:
         for i, (first, n) in enumerate(shard_ranges(a.first_rep, a.reps, a.shard_reps)):
             arrays = eng.export(0, a.seed, first, n, fields=fields, dtype=np.dtype(a.dtype))
             if a.stages:
                 st = eng.export_stages(0, a.seed, first, n, dtype=np.dtype(a.dtype))
                 arrays.update({STAGE_NAMES[f]: v for f, v in st.items()})
+            if a.llr is not None:
+                arrays.update(eng.export_llr(0, a.seed, first, n, method=a.llr, dtype=np.dtype(a.dtype)))
             print("wrote", write_shard(shard_path(a.out, i), arrays, dict(base, first_rep=int(first), n_rep=int(n))),
                   flush=True)
     finally:

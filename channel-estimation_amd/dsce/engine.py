@@ -25,6 +25,7 @@ EXPORTED = [
     "dsce_scheme_dims", "dsce_path_info", "dsce_set_option", "dsce_get_option", "dsce_fp64_mfma_peak",
     "dsce_kernel_work", "dsce_structured_check", "dsce_create_multi", "dsce_group_info",
     "dsce_transmission_matrix", "dsce_jakes_info", "dsce_export", "dsce_export_stages",
+    "dsce_llr_awgn", "dsce_export_llr", "dsce_llr_info",
 ]
 
 ABI_VERSION = 10
@@ -37,6 +38,11 @@ EXPORT_FIELDS = ("y", "hp_ls", "h_est", "h", "xp", "sym")
 # dsce_export_stages fields in the order of dsce_export_stages_out
 STAGE_FIELDS = ("hp_ls", "h_est", "y_ic", "dec_est", "dec_perf")
 _STAGE_INT = ("dec_est", "dec_perf")
+# dsce_llr_awgn / dsce_export_llr (include/dsce.h DSCE_LLR_MAXLOG; DSCE_HAS_LLR)
+LLR_MAXLOG = 1 << 2
+# dsce_export_llr fields in the order of dsce_export_llr_out
+LLR_FIELDS = ("x_est", "pn_eff", "llr")
+LLR_METHODS = {"exact": 0, "maxlog": LLR_MAXLOG}
 
 # dsce_jakes_info kernels (include/dsce.h DSCE_JAKES_*)
 JAKES_KERNELS = {0: "none", 1: "static", 2: "discrete", 3: "full", 4: "win_rec", 5: "win_mom", 6: "win_grp"}
@@ -91,6 +97,10 @@ class ExportOut(C.Structure):
 class ExportStagesOut(C.Structure):
     _fields_ = [("hp_ls", C.c_void_p), ("h_est", C.c_void_p), ("y_ic", C.c_void_p),
                 ("dec_est", C.POINTER(C.c_int32)), ("dec_perf", C.POINTER(C.c_int32))]
+
+
+class ExportLlrOut(C.Structure):
+    _fields_ = [("x_est", C.c_void_p), ("pn_eff", C.c_void_p), ("llr", C.c_void_p)]
 
 
 class TxDesc(C.Structure):
@@ -159,6 +169,10 @@ def load_library(path=None):
     lib.dsce_export.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(ExportOut)]
     lib.dsce_export_stages.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
                                        C.POINTER(ExportStagesOut)]
+    lib.dsce_llr_awgn.argtypes = [vp, C.c_int32, C.c_uint32, dp, dp, C.c_int64, C.c_int64, dp]
+    lib.dsce_export_llr.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                    C.POINTER(ExportLlrOut)]
+    lib.dsce_llr_info.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32)]
     for name in EXPORTED:
         fn = getattr(lib, name)
         if name != "dsce_last_error":
@@ -502,6 +516,95 @@ class Engine:
         self._export_stages(sid, seed, first_rep, n_rep,
                             EXPORT_DEVICE | (EXPORT_F32 if dtype == torch.complex64 else 0),
                             {f: t.data_ptr() for f, t in out.items()})
+        return out
+
+    # -- soft outputs (DSCE_HAS_LLR) ----------------------------------------------
+    @staticmethod
+    def _llr_flag(method):
+        if method not in LLR_METHODS:
+            raise ValueError("LLR method must be 'exact' or 'maxlog'")
+        return LLR_METHODS[method]
+
+    def llr_info(self, sid):
+        """dict(per_axis, m) of scheme sid's demapper (dsce_llr_info): per_axis =
+        every bit of the label depends on one axis of the constellation grid, so
+        the LLRs are PAM LLRs per axis; else the full-table form runs."""
+        out = (C.c_int32 * 2)()
+        self._chk(self.lib.dsce_llr_info(self.h, int(sid), out), "dsce_llr_info")
+        return dict(per_axis=bool(out[0]), m=int(out[1]))
+
+    def llr_awgn(self, sid, x, pn, method="exact"):
+        """SignalConstellation.LLR_AWGN of scheme sid's constellation on the GPU
+        (dsce_llr_awgn): x complex [n], pn a scalar or [n]; returns [n][m] float64,
+        positive = bit 1.  The arithmetic of export_llr."""
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.complex128).reshape(-1))
+        pn = np.ascontiguousarray(np.asarray(pn, dtype=np.float64).reshape(-1))
+        out = np.zeros((x.size, self.llr_info(sid)["m"]))
+        self._chk(self.lib.dsce_llr_awgn(self.h, int(sid), self._llr_flag(method), _dptr(x.view(np.float64)),
+                                         _dptr(pn), pn.size, x.size, _dptr(out)), "dsce_llr_awgn")
+        return out
+
+    def export_llr_shapes(self, sid, n_rep):
+        """Shapes of dsce_export_llr's arrays for n_rep realisations of scheme sid
+        (S = 1 + n_iter stages, m bits per symbol)."""
+        d = self.scheme_dims(sid)
+        n, S = int(n_rep), d.n_iter + 1
+        base = (n, d.n_snr, S, d.n_data)
+        return dict(x_est=base, pn_eff=base, llr=base + (self.llr_info(sid)["m"],))
+
+    def _export_llr(self, sid, seed, first_rep, n_rep, flags, ptrs):
+        bad = [f for f in ptrs if f not in LLR_FIELDS]
+        if bad:
+            raise ValueError("unknown LLR export field(s) %s (of %s)" % (bad, list(LLR_FIELDS)))
+        o = ExportLlrOut()
+        for f, p in ptrs.items():
+            setattr(o, f, p)
+        self._chk(self.lib.dsce_export_llr(self.h, int(sid), int(seed), int(first_rep), int(n_rep), int(flags),
+                                           C.byref(o)), "dsce_export_llr")
+
+    def export_llr(self, sid, seed, first_rep, n_rep, fields=LLR_FIELDS, method="exact", dtype=np.complex128):
+        """Soft outputs of the MMSE branch for realisations [first_rep, first_rep +
+        n_rep) of scheme sid, every SNR point and stage (dsce_export_llr) as a dict
+        of NumPy arrays: the demapper input x_est [n_rep][n_snr][S][ND] (dtype
+        complex128, or complex64: DSCE_EXPORT_F32), its noise power pn_eff (same
+        shape, float64 / float32) and llr [n_rep][n_snr][S][ND][m], positive = bit
+        1, method 'exact' (log-sum-exp) or 'maxlog'.  Realisation rep is
+        realisation rep of run(), export() and export_stages() with the same seed."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.complex128), np.dtype(np.complex64)):
+            raise ValueError("export dtype must be complex128 or complex64")
+        f32 = dt == np.dtype(np.complex64)
+        rdt = np.dtype(np.float32 if f32 else np.float64)
+        shapes = self.export_llr_shapes(sid, n_rep)
+        out = {f: np.zeros(shapes[f], dtype=dt if f == "x_est" else rdt) for f in fields}
+        self._export_llr(sid, seed, first_rep, n_rep, self._llr_flag(method) | (EXPORT_F32 if f32 else 0),
+                         {f: a.ctypes.data for f, a in out.items()})
+        return out
+
+    def export_llr_torch(self, sid, seed, first_rep, n_rep, fields=LLR_FIELDS, method="exact", dtype=None,
+                         device=None):
+        """export_llr() into torch tensors on the context's GPU, written by the
+        kernel itself (DSCE_EXPORT_DEVICE); dtype torch.complex128 (x_est; pn_eff
+        and llr float64) or torch.complex64 (float32).  See export_torch for
+        device and the import order of torch and the engine."""
+        import torch
+        dtype = torch.complex128 if dtype is None else dtype
+        if dtype not in (torch.complex128, torch.complex64):
+            raise ValueError("export_llr_torch dtype must be torch.complex128 or torch.complex64")
+        if not torch.cuda.is_available():
+            raise DsceError("export_llr_torch: torch sees no HIP device in this process; import torch before the "
+                            "first dsce.engine.Engine is created so that both use one HIP runtime")
+        if device is None:
+            device = self.group_info()[0][0]
+        f32 = dtype == torch.complex64
+        rdt = torch.float32 if f32 else torch.float64
+        shapes = self.export_llr_shapes(sid, n_rep)
+        dev = "cuda:%d" % int(device)
+        out = {f: torch.empty(shapes[f], dtype=dtype if f == "x_est" else rdt, device=dev) for f in fields}
+        torch.cuda.current_stream(dev).synchronize()
+        self._export_llr(sid, seed, first_rep, n_rep,
+                         EXPORT_DEVICE | self._llr_flag(method) | (EXPORT_F32 if f32 else 0),
+                         {f: t.data_ptr() for f, t in out.items()})
         return out
 
     # -- engine state ------------------------------------------------------------

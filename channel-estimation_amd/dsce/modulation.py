@@ -376,3 +376,48 @@ class SignalConstellation:
 
     def SymbolQuantization(self, EstimatedDataSymbols):
         return self.SymbolMapping[self._nearest(EstimatedDataSymbols)]
+
+    def LLR_AWGN(self, y, Pn, method="exact"):
+        """Per-bit LLRs of y = x + n, n complex Gaussian of power Pn (scalar or one
+        per symbol): [n][BitsPerSymbol], positive means bit 1
+        (SignalConstellation.m:103-122), see llr_awgn."""
+        return llr_awgn(self.SymbolMapping, self.BitMapping, y, Pn, method)
+
+
+def llr_awgn(symbols, bitmap, y, Pn, method="exact"):
+    """LLRs of the observations y over the constellation `symbols` [M] with bit
+    labels `bitmap` [M][m], noise power Pn (scalar or per observation):
+
+        exact:   log sum_{bit=1} exp(-|y - s|^2 / Pn) - log sum_{bit=0} exp(-|y - s|^2 / Pn)
+        maxlog:  (min_{bit=0} |y - s|^2 - min_{bit=1} |y - s|^2) / Pn
+
+    The exact form is the formula of SignalConstellation.m:118 evaluated with
+    each sum shifted by its own largest term (log-sum-exp), so it stays finite
+    where the literal formula gives +-Inf or 0/0 (which the reference patches
+    with +-1e10).  NaN in gives NaN out.  Returns [n][m] float64; the definition
+    that dsce_llr_awgn / dsce_export_llr (include/dsce.h) implement on the GPU."""
+    if method not in ("exact", "maxlog"):
+        raise ValueError("method must be 'exact' or 'maxlog'")
+    s = np.asarray(symbols, dtype=complex).reshape(-1)
+    bm = np.asarray(bitmap).astype(bool).reshape(s.size, -1)
+    y = np.asarray(y, dtype=complex).reshape(-1)
+    pn = np.asarray(Pn, dtype=float).reshape(-1)
+    if pn.size not in (1, y.size):
+        raise ValueError("Pn must be a scalar or one value per symbol")
+    pn = np.broadcast_to(pn, y.shape)
+    out = np.empty((y.size, bm.shape[1]))
+    for a in range(0, y.size, 16384):                      # n x M work arrays in bounded pieces
+        yy, pp = y[a:a + 16384, None], pn[a:a + 16384, None]
+        d = yy - s[None, :]
+        d2 = d.real * d.real + d.imag * d.imag
+        for b in range(bm.shape[1]):
+            one, zero = d2[:, bm[:, b]], d2[:, ~bm[:, b]]
+            if method == "maxlog":
+                out[a:a + 16384, b] = ((zero.min(axis=1, keepdims=True) - one.min(axis=1, keepdims=True)) / pp)[:, 0]
+                continue
+            e1, e0 = one / pp, zero / pp
+            m1, m0 = e1.min(axis=1, keepdims=True), e0.min(axis=1, keepdims=True)
+            with np.errstate(invalid="ignore"):
+                out[a:a + 16384, b] = ((m0 - m1) + np.log(np.exp(-(e1 - m1)).sum(axis=1, keepdims=True))
+                                       - np.log(np.exp(-(e0 - m0)).sum(axis=1, keepdims=True)))[:, 0]
+    return out

@@ -36,6 +36,9 @@
  *                            hP_LS, h_hat, y after interference cancellation and
  *                            the detected symbols of both CSI branches
  *                                                               script:412-453, :482-548
+ *   dsce_llr_awgn         <- SignalConstellation.LLR_AWGN        SignalConstellation.m:103-122
+ *   dsce_export_llr       <- the same applied to the demapper input of every stage
+ *                            of the MMSE branch                  script:429-444, :519-525
  *
  * Conventions
  *  - Return 0 on success, a negative DSCE_E* code on failure; the message is
@@ -81,6 +84,8 @@
  * in bulk.  Every ABI 8 entry point is unchanged.
  * ABI 10 adds dsce_export_stages (dsce_export_stages_out): the per-stage IC
  * data of every realisation in bulk.  Every ABI 9 entry point is unchanged.
+ * DSCE_HAS_LLR (still ABI 10: purely additive) announces dsce_llr_awgn,
+ * dsce_export_llr and dsce_llr_info: soft outputs of the demapper.
  */
 #ifndef DSCE_H
 #define DSCE_H
@@ -437,6 +442,79 @@ typedef struct {            /* every pointer optional; C order, element fastest;
  * bad device pointer.  On a multi-device handle the export is member 0's. */
 int dsce_export_stages(dsce_ctx* ctx, int32_t scheme_id, uint64_t seed, uint64_t first_rep, uint64_t n_rep,
                        uint32_t flags, const dsce_export_stages_out* out);
+
+/* ---- soft outputs (DSCE_HAS_LLR; additive, the ABI version stays 10) ------ */
+/* Definitions.
+ *  Symbol table: symbols[0..M-1] of the scheme, sorted by bit label; bit b of
+ *  symbol index i is (i >> b) & 1 (bi2de, LSB first, as the BITS stream and sym
+ *  of dsce_export); m = bits_per_symbol.
+ *  Exact LLR (SignalConstellation.LLR_AWGN, its sign: positive means bit 1):
+ *    LLR_b(x, pn) = log sum_{i: bit_b(i)=1} exp(-|x - s_i|^2 / pn)
+ *                 - log sum_{i: bit_b(i)=0} exp(-|x - s_i|^2 / pn),
+ *  evaluated in a max-shifted (log-sum-exp) form: finite and accurate for every
+ *  finite x and every pn > 0.  The literal formula underflows to +-Inf or 0/0 far
+ *  from the constellation or at small pn (about 8 % of the entries of a default
+ *  10 dB / 35 dB export), which the reference patches with +-1e10
+ *  (SignalConstellation.m:120-121); the engine returns the true finite value.
+ *  NaN inputs give NaN.
+ *  Max-log LLR (DSCE_LLR_MAXLOG):
+ *    LLR_b = (min_{bit_b=0} |x - s_i|^2 - min_{bit_b=1} |x - s_i|^2) / pn.
+ *  Demapper input of the MMSE branch, stage s, data symbol j (what the stage
+ *  kernels slice, script:429-444, :519-525), with Pn_l = pn_time[snr] ||Q[:, l]||^2
+ *  the AWGN power of y_l:
+ *    select schemes (OFDM, FBMC auxiliary; l = data_pos[j]):
+ *      x_est_j  = y_ic,s[l] / h_est,s[l] / data_div
+ *      pn_eff_j = Pn_l / (|h_est,s[l]|^2 data_div^2)
+ *    despread schemes (FBMC coded):
+ *      x_est_j  = sum_l conj(P[l, NP+j]) y_ic,s[l] / h_est,s[l] / data_div
+ *      pn_eff_j = sum_l |P[l, NP+j]|^2 Pn_l / |h_est,s[l]|^2 / data_div^2
+ *  With real_detect x_est is the real part (imaginary part stored as 0); pn_eff
+ *  stays the complex power: for a real observation exp(-d^2 / pn) is then the
+ *  Gaussian density of variance pn / 2, which is what LLR_AWGN assumes.  Stage 0
+ *  uses y_ic = y; h_est follows the W / W0 switch as in dsce_export_stages.
+ *  This is the AWGN model of LLR_AWGN: the residual interference and the
+ *  correlation of the noise between positions are ignored. */
+#define DSCE_HAS_LLR 1
+#define DSCE_LLR_MAXLOG (1u << 2)      /* shares the flags word of DSCE_EXPORT_* */
+
+/* SignalConstellation.LLR_AWGN (SignalConstellation.m:103-122) of a scheme's
+ * constellation: x n complex (interleaved), pn n_pn = 1 (scalar) or n real,
+ * llr_out [n][m] doubles.  Needs only dsce_add_scheme.  flags: 0 |
+ * DSCE_LLR_MAXLOG.  The arithmetic is the device function of dsce_export_llr.
+ * DSCE_EINVAL for null pointers with n > 0, n < 0, n_pn neither 1 nor n, or an
+ * unknown flag; n = 0 does nothing. */
+int dsce_llr_awgn(dsce_ctx* ctx, int32_t scheme_id, uint32_t flags, const double* x, const double* pn,
+                  int64_t n_pn, int64_t n, double* llr_out);
+
+typedef struct {          /* every pointer optional; C order; S = 1 + n_iter */
+    void* x_est;          /* [n_rep][n_snr][S][ND]     complex */
+    void* pn_eff;         /* [n_rep][n_snr][S][ND]     real    */
+    void* llr;            /* [n_rep][n_snr][S][ND][m]  real    */
+} dsce_export_llr_out;
+
+/* The sibling of dsce_export_stages for the soft outputs of the MMSE branch:
+ * the same run of the stage kernels (realisation `rep` is realisation `rep` of
+ * dsce_run, dsce_export and dsce_export_stages with the same seed), then "k_llr"
+ * (its name under dsce_enable_timing) forms x_est, pn_eff and the LLRs as
+ * defined above from the staged y_ic and h_est of every stage.  Batches, SNR
+ * chunks, the export_stage_mb cut, padding realisations, any n_rep >= 0 and the
+ * absence of side effects are those of dsce_export_stages.  flags:
+ * DSCE_EXPORT_F32 (x_est complex64, pn_eff and llr float, each fp64 value
+ * rounded once at the store), DSCE_EXPORT_DEVICE, DSCE_LLR_MAXLOG.  DSCE_ESTATE
+ * before channel, SNR points or scheme are set, and without dsce_build_mmse (an
+ * interpolation scheme with n_iter == 0 needs none).  DSCE_EINVAL for a null
+ * out, no field requested, an unknown flag or a bad device pointer.  On a
+ * multi-device handle the export is member 0's.  The LLRs of the perfect-CSI
+ * branch are not exported: form x_est / pn_eff from dsce_export's y and h and
+ * call dsce_llr_awgn. */
+int dsce_export_llr(dsce_ctx* ctx, int32_t scheme_id, uint64_t seed, uint64_t first_rep, uint64_t n_rep,
+                    uint32_t flags, const dsce_export_llr_out* out);
+
+/* Which form the demapper of a scheme takes: out2[0] = 1 the per-axis form
+ * (every bit of the label depends on one axis of the constellation grid only:
+ * the LLR is a PAM LLR over that axis' levels; every Gray map of the reference),
+ * 0 the full-table form over all M symbols; out2[1] = m. */
+int dsce_llr_info(dsce_ctx* ctx, int32_t scheme_id, int32_t* out2);
 
 /* ---- engine state ------------------------------------------------------- */
 int dsce_scheme_dims(dsce_ctx* ctx, int32_t scheme_id, dsce_dims* dims);
