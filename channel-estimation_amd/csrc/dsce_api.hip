@@ -243,6 +243,39 @@ void free_alloc(dsce_ctx* c, void* p) {
         }
 }
 
+// Device memory that lives for one call.  One rule on every exit, an exception
+// included: synchronise the context's stream (work queued on it may still read
+// or write the memory), then free.  The destructor does so and ignores the
+// results; release_checked() is the same on the success path and reports what
+// failed.  A zero-byte request allocates one byte.  A host buffer that queued
+// copies fill is declared before the holder, so that it outlives the wait.
+struct DeviceTemps {
+    dsce_ctx* c;
+    std::vector<void*> ptrs;
+    explicit DeviceTemps(dsce_ctx* ctx) : c(ctx) {}
+    DeviceTemps(const DeviceTemps&) = delete;
+    DeviceTemps& operator=(const DeviceTemps&) = delete;
+    template <class T>
+    T* alloc(size_t n) {
+        ptrs.push_back(nullptr);
+        DSCE_HIP_CHECK(hipMalloc(&ptrs.back(), std::max<size_t>(n * sizeof(T), 1)));
+        return (T*)ptrs.back();
+    }
+    void release_checked() {
+        DSCE_HIP_CHECK(hipStreamSynchronize(c->stream));
+        while (!ptrs.empty()) {
+            void* p = ptrs.back();
+            ptrs.pop_back();
+            DSCE_HIP_CHECK(hipFree(p));
+        }
+    }
+    ~DeviceTemps() {
+        if (ptrs.empty()) return;
+        (void)hipStreamSynchronize(c->stream);
+        for (void* p : ptrs) (void)hipFree(p);
+    }
+};
+
 hipEvent_t get_event(dsce_ctx* c) {
     if (!c->event_pool.empty()) {
         hipEvent_t e = c->event_pool.back();
@@ -839,13 +872,11 @@ void pack_scheme(dsce_ctx* c, Scheme& s) {
 // only skips exact zeros, so results are bit-identical; at C3/C4 the thresholded
 // estimator spans |dk| <= 7 symbols instead of the structural 15.
 // ---------------------------------------------------------------------------
-void trim_w_band(dsce_ctx* c, Scheme& s, std::vector<void*>& tmp) {
+void trim_w_band(dsce_ctx* c, Scheme& s, DeviceTemps& tmp) {
     if (!c->op.wtrim) return;                    // Opts::wtrim = 0 keeps the structural band
     hipStream_t st = c->stream;
     const int NP = s.d.n_pilots, nsl = 2 * c->nsnr, nblk = (int)s.wband.row0.size();
-    int* dlohi;
-    DSCE_HIP_CHECK(hipMalloc(&dlohi, 2 * nblk * sizeof(int)));
-    tmp.push_back(dlohi);
+    int* dlohi = tmp.alloc<int>(2 * (size_t)nblk);
     std::vector<int> lohi(2 * nblk);
     for (int b = 0; b < nblk; ++b) {
         lohi[2 * b] = 1 << 30;
@@ -1285,13 +1316,7 @@ void build_mic(dsce_ctx* c, Scheme& s, const SetupArgs& a, const double2* m, con
 void build_mmse(dsce_ctx* c, Scheme& s, double thr) {
     hipStream_t st = c->stream;
     const int N = s.N, LK = s.LK, NP = s.d.n_pilots, Nsym = s.d.n_tx_symbols, nsnr = c->nsnr;
-    std::vector<void*> tmp;
-    auto talloc = [&](size_t bytes) {
-        void* p;
-        DSCE_HIP_CHECK(hipMalloc(&p, bytes));
-        tmp.push_back(p);
-        return p;
-    };
+    DeviceTemps tmp(c);
     if (s.W) {                     // rebuild (e.g. new SNR list): back to the structural band
         free_alloc(c, s.W);
         free_alloc(c, s.Wd);
@@ -1321,106 +1346,101 @@ void build_mmse(dsce_ctx* c, Scheme& s, double thr) {
         s.w_elems = s.wband.elems;
         s.Wb = upload_band(c, s.wband, false);
     }
-    try {
-        double2* dG = (double2*)talloc(s.G.size() * sizeof(double2));
-        double2* dQ = (double2*)talloc(s.Q.size() * sizeof(double2));
-        double2* dP = (double2*)talloc(s.P.size() * sizeof(double2));
-        DSCE_HIP_CHECK(hipMemcpy(dG, s.G.data(), s.G.size() * sizeof(double2), hipMemcpyHostToDevice));
-        DSCE_HIP_CHECK(hipMemcpy(dQ, s.Q.data(), s.Q.size() * sizeof(double2), hipMemcpyHostToDevice));
-        DSCE_HIP_CHECK(hipMemcpy(dP, s.P.data(), s.P.size() * sizeof(double2), hipMemcpyHostToDevice));
-        int* dpil = (int*)talloc(NP * sizeof(int));
-        DSCE_HIP_CHECK(hipMemcpy(dpil, s.pilot_pos.data(), NP * sizeof(int), hipMemcpyHostToDevice));
-        double* j0tab = (double*)talloc((2 * N - 1) * sizeof(double));
-        if (c->ch.model >= 2 && c->ch.fD > 0)     // FastFading.m:331-336: no TimeCorrelation for 'Discrete-*'
-            throw ApiError(DSCE_EINVAL, "the time correlation (and so the MMSE estimator) is undefined for a "
-                                        "discrete Doppler spectrum (FastFading.m:321-336)");
-        setup_time_correlation(st, N, c->ch.fD, c->ch.dt, c->ch.model, j0tab);
-        SetupArgs a{};
-        a.N = N;
-        a.LK = LK;
-        a.NP = NP;
-        a.Nsym = Nsym;
-        a.ntap = c->ch.ntap;
-        a.nsnr = nsnr;
-        a.pilot_pos = dpil;
-        a.G = dG;
-        a.Q = dQ;
-        a.P = dP;
-        a.j0tab = j0tab;
-        for (int q = 0; q < c->ch.ntap; ++q) {
-            a.tap_delay[q] = c->ch.tap_delay[q];
-            a.pdp[q] = c->pdp_norm[c->ch.tap_delay[q]];
-        }
-        a.kappa = s.d.kappa;
-        a.thr = thr;
-        double2* m = (double2*)talloc((size_t)NP * a.ntap * N * sizeof(double2));
-        setup_mcoef(st, a, s.k.g_start, s.GL, s.k.q_start, s.QL, m);
-        double2* rhp = (double2*)talloc((size_t)NP * NP * sizeof(double2));
-        setup_rhp(st, a, m, rhp);
-        double2* gp = (double2*)talloc((size_t)N * Nsym * sizeof(double2));
-        setup_gp(st, a, gp);
-        double* dg = (double*)talloc(NP * sizeof(double));
-        setup_rest_diag(st, a, gp, s.k.q_start, s.QL, dg);
-        std::vector<double2> hrhp((size_t)NP * NP);
-        std::vector<double> hdiag(NP);
-        DSCE_HIP_CHECK(hipMemcpyAsync(hrhp.data(), rhp, hrhp.size() * sizeof(double2), hipMemcpyDeviceToHost, st));
-        DSCE_HIP_CHECK(hipMemcpyAsync(hdiag.data(), dg, NP * sizeof(double), hipMemcpyDeviceToHost, st));
-        DSCE_HIP_CHECK(hipStreamSynchronize(st));
-        // R_est / R_noI per SNR (script:238-253): tiny NP x NP assembly on the host
-        std::vector<double> qn(NP, 0.0);
-        for (int i = 0; i < NP; ++i) {
-            const int col = s.pilot_pos[i];
-            double acc = 0.0;
-            for (int n = 0; n < N; ++n) {
-                const double2 q = s.Q[(size_t)col * N + n];
-                acc += q.x * q.x + q.y * q.y;
-            }
-            qn[i] = acc;
-        }
-        s.R_hP = hrhp;
-        s.R_est.assign((size_t)nsnr * NP * NP, make_double2(0, 0));
-        s.R_noI.assign((size_t)nsnr * NP * NP, make_double2(0, 0));
-        for (int k = 0; k < nsnr; ++k) {
-            for (int j = 0; j < NP; ++j)
-                for (int i = 0; i < NP; ++i) {
-                    const size_t ix = (size_t)j * NP + i;
-                    double2 noN = i == j ? make_double2(hdiag[i], 0.0) : hrhp[ix];
-                    double2 est = noN;
-                    if (i == j) est.x = hdiag[i] + c->pn[k] * qn[i] / s.d.kappa;
-                    s.R_est[(size_t)k * NP * NP + ix] = est;
-                    // R_est - (R_est_noNoise - R_hP)
-                    const double2 diff = c_sub(noN, hrhp[ix]);
-                    s.R_noI[(size_t)k * NP * NP + ix] = c_sub(est, diff);
-                }
-        }
-        // inverses: [var][snr]
-        double2* dR = (double2*)talloc((size_t)2 * nsnr * NP * NP * sizeof(double2));
-        double2* dRi = (double2*)talloc((size_t)2 * nsnr * NP * NP * sizeof(double2));
-        DSCE_HIP_CHECK(hipMemcpy(dR, s.R_est.data(), (size_t)nsnr * NP * NP * sizeof(double2), hipMemcpyHostToDevice));
-        DSCE_HIP_CHECK(hipMemcpy(dR + (size_t)nsnr * NP * NP, s.R_noI.data(), (size_t)nsnr * NP * NP * sizeof(double2),
-                                 hipMemcpyHostToDevice));
-        setup_rinv(st, NP, 2 * nsnr, dR, dRi);
-        // R_Dij packed, then W / W0 per SNR
-        double2* rd = (double2*)talloc((size_t)s.w_elems * sizeof(double2));
-        Band Wb = s.Wb;
-        setup_rdij(st, a, Wb, m, s.k.g_start, s.GL, s.k.q_start, s.QL, rd);
-        s.W = dalloc<double2>(c, (size_t)2 * nsnr * s.w_elems);
-        s.Wd = dalloc<double2>(c, (size_t)2 * nsnr * LK * NP);
-        for (int var = 0; var < 2; ++var)
-            for (int k = 0; k < nsnr; ++k) {
-                const size_t vi = (size_t)var * nsnr + k;
-                setup_w(st, a, Wb, s.w_elems, rd, dRi + vi * NP * NP, s.W + vi * s.w_elems, s.Wd + vi * LK * NP);
-            }
-        DSCE_HIP_CHECK(hipStreamSynchronize(st));
-        DSCE_HIP_CHECK(hipGetLastError());
-        trim_w_band(c, s, tmp);
-        build_wpair(c, s);
-        build_mic(c, s, a, m, dRi);
-    } catch (...) {
-        for (void* p : tmp) (void)hipFree(p);
-        throw;
+    double2* dG = tmp.alloc<double2>(s.G.size());
+    double2* dQ = tmp.alloc<double2>(s.Q.size());
+    double2* dP = tmp.alloc<double2>(s.P.size());
+    DSCE_HIP_CHECK(hipMemcpy(dG, s.G.data(), s.G.size() * sizeof(double2), hipMemcpyHostToDevice));
+    DSCE_HIP_CHECK(hipMemcpy(dQ, s.Q.data(), s.Q.size() * sizeof(double2), hipMemcpyHostToDevice));
+    DSCE_HIP_CHECK(hipMemcpy(dP, s.P.data(), s.P.size() * sizeof(double2), hipMemcpyHostToDevice));
+    int* dpil = tmp.alloc<int>(NP);
+    DSCE_HIP_CHECK(hipMemcpy(dpil, s.pilot_pos.data(), NP * sizeof(int), hipMemcpyHostToDevice));
+    double* j0tab = tmp.alloc<double>(2 * N - 1);
+    if (c->ch.model >= 2 && c->ch.fD > 0)     // FastFading.m:331-336: no TimeCorrelation for 'Discrete-*'
+        throw ApiError(DSCE_EINVAL, "the time correlation (and so the MMSE estimator) is undefined for a "
+                                    "discrete Doppler spectrum (FastFading.m:321-336)");
+    setup_time_correlation(st, N, c->ch.fD, c->ch.dt, c->ch.model, j0tab);
+    SetupArgs a{};
+    a.N = N;
+    a.LK = LK;
+    a.NP = NP;
+    a.Nsym = Nsym;
+    a.ntap = c->ch.ntap;
+    a.nsnr = nsnr;
+    a.pilot_pos = dpil;
+    a.G = dG;
+    a.Q = dQ;
+    a.P = dP;
+    a.j0tab = j0tab;
+    for (int q = 0; q < c->ch.ntap; ++q) {
+        a.tap_delay[q] = c->ch.tap_delay[q];
+        a.pdp[q] = c->pdp_norm[c->ch.tap_delay[q]];
     }
-    for (void* p : tmp) DSCE_HIP_CHECK(hipFree(p));
+    a.kappa = s.d.kappa;
+    a.thr = thr;
+    double2* m = tmp.alloc<double2>((size_t)NP * a.ntap * N);
+    setup_mcoef(st, a, s.k.g_start, s.GL, s.k.q_start, s.QL, m);
+    double2* rhp = tmp.alloc<double2>((size_t)NP * NP);
+    setup_rhp(st, a, m, rhp);
+    double2* gp = tmp.alloc<double2>((size_t)N * Nsym);
+    setup_gp(st, a, gp);
+    double* dg = tmp.alloc<double>(NP);
+    setup_rest_diag(st, a, gp, s.k.q_start, s.QL, dg);
+    std::vector<double2> hrhp((size_t)NP * NP);
+    std::vector<double> hdiag(NP);
+    DSCE_HIP_CHECK(hipMemcpyAsync(hrhp.data(), rhp, hrhp.size() * sizeof(double2), hipMemcpyDeviceToHost, st));
+    DSCE_HIP_CHECK(hipMemcpyAsync(hdiag.data(), dg, NP * sizeof(double), hipMemcpyDeviceToHost, st));
+    DSCE_HIP_CHECK(hipStreamSynchronize(st));
+    // R_est / R_noI per SNR (script:238-253): tiny NP x NP assembly on the host
+    std::vector<double> qn(NP, 0.0);
+    for (int i = 0; i < NP; ++i) {
+        const int col = s.pilot_pos[i];
+        double acc = 0.0;
+        for (int n = 0; n < N; ++n) {
+            const double2 q = s.Q[(size_t)col * N + n];
+            acc += q.x * q.x + q.y * q.y;
+        }
+        qn[i] = acc;
+    }
+    s.R_hP = hrhp;
+    s.R_est.assign((size_t)nsnr * NP * NP, make_double2(0, 0));
+    s.R_noI.assign((size_t)nsnr * NP * NP, make_double2(0, 0));
+    for (int k = 0; k < nsnr; ++k) {
+        for (int j = 0; j < NP; ++j)
+            for (int i = 0; i < NP; ++i) {
+                const size_t ix = (size_t)j * NP + i;
+                double2 noN = i == j ? make_double2(hdiag[i], 0.0) : hrhp[ix];
+                double2 est = noN;
+                if (i == j) est.x = hdiag[i] + c->pn[k] * qn[i] / s.d.kappa;
+                s.R_est[(size_t)k * NP * NP + ix] = est;
+                // R_est - (R_est_noNoise - R_hP)
+                const double2 diff = c_sub(noN, hrhp[ix]);
+                s.R_noI[(size_t)k * NP * NP + ix] = c_sub(est, diff);
+            }
+    }
+    // inverses: [var][snr]
+    double2* dR = tmp.alloc<double2>((size_t)2 * nsnr * NP * NP);
+    double2* dRi = tmp.alloc<double2>((size_t)2 * nsnr * NP * NP);
+    DSCE_HIP_CHECK(hipMemcpy(dR, s.R_est.data(), (size_t)nsnr * NP * NP * sizeof(double2), hipMemcpyHostToDevice));
+    DSCE_HIP_CHECK(hipMemcpy(dR + (size_t)nsnr * NP * NP, s.R_noI.data(), (size_t)nsnr * NP * NP * sizeof(double2),
+                             hipMemcpyHostToDevice));
+    setup_rinv(st, NP, 2 * nsnr, dR, dRi);
+    // R_Dij packed, then W / W0 per SNR
+    double2* rd = tmp.alloc<double2>((size_t)s.w_elems);
+    Band Wb = s.Wb;
+    setup_rdij(st, a, Wb, m, s.k.g_start, s.GL, s.k.q_start, s.QL, rd);
+    s.W = dalloc<double2>(c, (size_t)2 * nsnr * s.w_elems);
+    s.Wd = dalloc<double2>(c, (size_t)2 * nsnr * LK * NP);
+    for (int var = 0; var < 2; ++var)
+        for (int k = 0; k < nsnr; ++k) {
+            const size_t vi = (size_t)var * nsnr + k;
+            setup_w(st, a, Wb, s.w_elems, rd, dRi + vi * NP * NP, s.W + vi * s.w_elems, s.Wd + vi * LK * NP);
+        }
+    DSCE_HIP_CHECK(hipStreamSynchronize(st));
+    DSCE_HIP_CHECK(hipGetLastError());
+    trim_w_band(c, s, tmp);
+    build_wpair(c, s);
+    build_mic(c, s, a, m, dRi);
+    tmp.release_checked();
     s.mmse_ready = true;
 }
 
@@ -1848,6 +1868,26 @@ int api_fail(dsce_ctx* c, int code, const std::string& msg) {
     return code;
 }
 
+// The std::exception in flight (call from its catch block) as the status code
+// an entry point returns for it, and its message
+int exception_status(std::string& msg) {
+    try {
+        throw;
+    } catch (const ApiError& e) {
+        msg = e.what();
+        return e.code;
+    } catch (const HipError& e) {
+        msg = e.what();
+        return DSCE_EHIP;
+    } catch (const std::bad_alloc&) {
+        msg = "host out of memory";
+        return DSCE_ENOMEM;
+    } catch (const std::exception& e) {
+        msg = e.what();
+        return DSCE_EINVAL;
+    }
+}
+
 // API_END: every entry point that launched work returns the launch errors it
 // left (check_ctx clears stale errors at entry, so an error not
 // checked before returning would otherwise be lost)
@@ -1855,11 +1895,172 @@ int api_fail(dsce_ctx* c, int code, const std::string& msg) {
 #define API_END                                                 \
     DSCE_HIP_CHECK(hipGetLastError());                          \
     }                                                           \
-    catch (const ApiError& e) { return api_fail(ctx, e.code, e.what()); } \
-    catch (const HipError& e) { return api_fail(ctx, DSCE_EHIP, e.what()); } \
-    catch (const std::bad_alloc&) { return api_fail(ctx, DSCE_ENOMEM, "host out of memory"); } \
-    catch (const std::exception& e) { return api_fail(ctx, DSCE_EINVAL, e.what()); }     \
+    catch (const std::exception&) {                             \
+        std::string msg_;                                       \
+        const int code_ = exception_status(msg_);               \
+        return api_fail(ctx, code_, msg_);                      \
+    }                                                           \
     return DSCE_OK;
+
+// Realisations [0, n_rep) in batches of at most `cap` (a multiple of 64):
+// body(done, R, nvalid) runs R of them from number `done`, of which the first
+// nvalid were asked for.  Any n_rep (the script's NrRepetitions, script:19 /
+// :44): a tail that is no multiple of 64 runs as a whole wave whose padding
+// realisations count nothing.
+template <class Body>
+void walk_batches(uint64_t n_rep, int cap, Body body) {
+    for (uint64_t done = 0; done < n_rep;) {
+        const uint64_t left = n_rep - done;
+        const int R = (int)std::min<uint64_t>((uint64_t)cap, (left + 63) / 64 * 64);
+        const int nvalid = (int)std::min<uint64_t>((uint64_t)R, left);
+        body(done, R, nvalid);
+        done += (uint64_t)nvalid;
+    }
+}
+
+// Where a bulk export (dsce_export, dsce_export_stages, dsce_export_llr) puts
+// its fields: the caller's arrays [n_rep][per_rep], which the export kernels
+// write in place (DSCE_EXPORT_DEVICE, the batch from realisation `done` at row
+// `done`), or else through the context's staging buffer, one batch at a time.
+struct ExportSink {
+    const char* what;           // the entry point's name, for messages
+    int n;                      // fields (<= 6), in the export kernel's order
+    void* dst[6];               // caller's destinations (null: not requested)
+    size_t per_rep[6];          // elements per realisation
+    size_t esz[6];              // bytes per element
+    bool to_device;
+    void* out[6];               // begin(): where the batch's kernels write each field ...
+    long long row0;             // ... and the row of out[] that its realisation 0 takes
+
+    size_t bytes(int i, uint64_t reps) const { return (size_t)reps * per_rep[i] * esz[i]; }
+
+    // A field is requested; ready() (the entry point's estimator precondition,
+    // which throws); device destinations are device memory of the context's GPU.
+    template <class Ready>
+    void check(dsce_ctx* ctx, Ready ready) const {
+        const std::string w(what);
+        bool any = false;
+        for (int i = 0; i < n; ++i) any = any || dst[i];
+        if (!any) throw ApiError(DSCE_EINVAL, w + ": no field requested");
+        ready();
+        for (int i = 0; to_device && i < n; ++i) {
+            if (!dst[i]) continue;
+            hipPointerAttribute_t at{};
+            const hipError_t e = hipPointerGetAttributes(&at, dst[i]);
+            if (e != hipSuccess) (void)hipGetLastError();
+            if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != ctx->device)
+                throw ApiError(DSCE_EINVAL, w + ": DSCE_EXPORT_DEVICE with a pointer that is not device "
+                                                "memory of the context's GPU");
+        }
+    }
+
+    // Before the kernels of the batch [done, done + nvalid): sets out[] and row0.
+    // Host destinations: every requested field of the batch, each 256-byte
+    // aligned, in ctx->exp_stage, which grows when a batch needs more (the stream
+    // may still read the old buffer: synchronise before freeing it).
+    void begin(dsce_ctx* ctx, uint64_t done, int nvalid) {
+        row0 = to_device ? (long long)done : 0;
+        size_t off[6], total = 0;
+        for (int i = 0; i < n; ++i) {
+            off[i] = total;
+            if (dst[i] && !to_device) total += (bytes(i, nvalid) + 255) / 256 * 256;
+        }
+        if (total && (!ctx->exp_stage || total > ctx->exp_stage_bytes)) {
+            if (ctx->exp_stage) {
+                DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+                DSCE_HIP_CHECK(hipFree(ctx->exp_stage));
+            }
+            ctx->exp_stage = nullptr;
+            DSCE_HIP_CHECK(hipMalloc(&ctx->exp_stage, total));
+            ctx->exp_stage_bytes = total;
+        }
+        for (int i = 0; i < n; ++i) out[i] = to_device || !dst[i] ? dst[i] : (char*)ctx->exp_stage + off[i];
+    }
+
+    // After them: the batch from the staging buffer to the host destinations
+    // (asynchronous: finish() waits).
+    void end(dsce_ctx* ctx, uint64_t done, int nvalid) const {
+        for (int i = 0; !to_device && i < n; ++i)
+            if (dst[i])
+                DSCE_HIP_CHECK(hipMemcpyAsync((char*)dst[i] + bytes(i, done), out[i], bytes(i, nvalid),
+                                              hipMemcpyDeviceToHost, ctx->stream));
+    }
+
+    // After the last batch.
+    void finish(dsce_ctx* ctx) const {
+        DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (ctx->timing) collect_timing(ctx);
+    }
+};
+
+// The entry checks of the three bulk exports, up to the fields (ExportSink::check)
+Scheme& bulk_export_check(dsce_ctx* ctx, int32_t id, const void* out, uint32_t flags, uint32_t allowed,
+                          const char* what) {
+    const std::string w(what);
+    if (!ctx->chan_set) throw ApiError(DSCE_ESTATE, "dsce_set_channel first");
+    if (ctx->nsnr <= 0) throw ApiError(DSCE_ESTATE, "dsce_set_snr first");
+    if (ctx->schemes.empty()) throw ApiError(DSCE_ESTATE, "no scheme added");
+    Scheme& s = get_scheme(ctx, id);
+    if (!out) throw ApiError(DSCE_EINVAL, w + ": null out");
+    if (flags & ~allowed) throw ApiError(DSCE_EINVAL, w + ": unknown flag");
+    return s;
+}
+
+// The bulk exports behind run_batch (dsce_export_stages, dsce_export_llr): their
+// estimator precondition and fields checked, then run_batch for scheme `id` with
+// the stage kernels in TraceK's bulk mode (struct Bulk), `launch` after each SNR
+// chunk.  Scratch counters, no MSE sums, Scheme::path restored.  A batch is cut
+// into sub-batches of whole waves so that the bulk arrays stay within option
+// export_stage_mb (every realisation is its own Philox streams: the cut does not
+// show).  launch(bk, snr0): the export kernel of the chunk that starts at SNR
+// index snr0, from the bulk arrays of bk into the sink's out[] at row0, for the
+// sub-batch in ctx->buf (R, rvalid, U).
+template <class Launch>
+void bulk_export(dsce_ctx* ctx, Scheme& s, int32_t id, uint64_t seed, uint64_t first_rep, uint64_t n_rep,
+                 ExportSink& sink, Launch launch) {
+    const std::string w(sink.what);
+    sink.check(ctx, [&] {
+        if (!(s.mmse_ready && s.Wd))
+            throw ApiError(DSCE_ESTATE, w + ": dsce_build_mmse first (or dsce_set_interpolation with n_iter 0)");
+        if (s.interp && ctx->niter > 0)
+            throw ApiError(DSCE_ESTATE, w + ": interference-cancellation iterations need the MMSE estimator "
+                                            "(n_iter must be 0 with an interpolation estimator)");
+    });
+    const int LK = s.LK, NP = s.d.n_pilots, ND = s.d.n_data, nsnr = ctx->nsnr, S = ctx->niter + 1;
+    // the bulk trace arrays of one unit: hP, diag(D_hat), y_ic and both decisions of every stage
+    const int chunk = snr_chunk(ctx);
+    const size_t unit_bytes = (size_t)S * (((size_t)NP + 2 * (size_t)LK) * sizeof(double2) + 2 * (size_t)ND * sizeof(int));
+    const size_t bound = (size_t)ctx->op.export_stage_mb << 20;
+    const size_t waves = std::max<size_t>(1, bound / (unit_bytes * 64 * (size_t)chunk));
+    const int rsub = (int)std::min<size_t>((size_t)(ctx->batch + 63) / 64, waves) * 64;
+    DeviceTemps tmp(ctx);
+    Bulk bk;
+    bk.scheme = id;
+    bk.units = (size_t)rsub * chunk;
+    bk.k.LK = LK;
+    bk.k.ND = ND;
+    bk.k.unit = 0;
+    bk.k.yperf = nullptr;
+    bk.k.yest = tmp.alloc<double2>(bk.units * S * LK);
+    bk.k.hest = tmp.alloc<double2>(bk.units * S * LK);
+    bk.k.dec_e = tmp.alloc<int>(bk.units * S * ND);
+    bk.k.dec_p = tmp.alloc<int>(bk.units * S * ND);
+    bk.hp = tmp.alloc<double2>(bk.units * S * NP);
+    bk.dev = tmp.alloc<TraceK>(1);
+    const size_t ncount = ctx->schemes.size() * 4 * (size_t)nsnr * S;
+    bk.counters = tmp.alloc<unsigned long long>(ncount);
+    DSCE_HIP_CHECK(hipMemsetAsync(bk.counters, 0, ncount * sizeof(unsigned long long), ctx->stream));
+    bk.flush = [&](int snr0) { launch(bk, snr0); };
+    walk_batches(n_rep, rsub, [&](uint64_t done, int R, int nvalid) {
+        ensure_buffers(ctx, ctx->batch);
+        ctx->buf.mse_err = ctx->buf.mse_pow = nullptr;
+        sink.begin(ctx, done, nvalid);
+        run_batch(ctx, seed, first_rep + done, R, nvalid, nullptr, &bk);
+        sink.end(ctx, done, nvalid);
+    });
+    sink.finish(ctx);
+    tmp.release_checked();
+}
 
 // Algorithmic work per realisation of one timed kernel group of a scheme
 // (dsce_kernel_work).  Flops: 8 per complex multiply-accumulate, 2 per real
@@ -2383,18 +2584,11 @@ static void collect_mse(dsce_ctx* ctx, std::vector<double>& dst) {
 // counters (zeroed first); nothing is copied back
 static void run_reps(dsce_ctx* ctx, uint64_t seed, uint64_t first_rep, uint64_t n_rep) {
     prepare_run(ctx);
-    // any n_rep (the script's NrRepetitions, script:19 / :44): a tail that is no
-    // multiple of 64 runs as a whole wave whose padding realisations count nothing
-    uint64_t done = 0;
-    while (done < n_rep) {
-        const uint64_t left = n_rep - done;
-        const int R = (int)std::min<uint64_t>((uint64_t)ctx->batch, (left + 63) / 64 * 64);
-        const int nvalid = (int)std::min<uint64_t>((uint64_t)R, left);
+    walk_batches(n_rep, ctx->batch, [&](uint64_t done, int R, int nvalid) {
         ensure_buffers(ctx, ctx->batch);
         set_mse_buffers(ctx);
         run_batch(ctx, seed, first_rep + done, R, nvalid, nullptr);
-        done += (uint64_t)nvalid;
-    }
+    });
 }
 
 // The member's device counters added into err_counts (null: none), its MSE sums
@@ -2434,18 +2628,8 @@ static void run_multi(dsce_ctx* ctx, uint64_t seed, uint64_t first_rep, uint64_t
             run_reps(c, seed, f, k);
             DSCE_HIP_CHECK(hipGetLastError());
             return;
-        } catch (const ApiError& e) {
-            code[m] = e.code;
-            msg[m] = e.what();
-        } catch (const HipError& e) {
-            code[m] = DSCE_EHIP;
-            msg[m] = e.what();
-        } catch (const std::bad_alloc&) {
-            code[m] = DSCE_ENOMEM;
-            msg[m] = "host out of memory";
-        } catch (const std::exception& e) {
-            code[m] = DSCE_EINVAL;
-            msg[m] = e.what();
+        } catch (const std::exception&) {
+            code[m] = exception_status(msg[m]);
         }
     };
     std::vector<std::thread> th;
@@ -2522,42 +2706,21 @@ int dsce_export(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, ui
     TraceRange trace_range("dsce export");
     API_BEGIN
     check_ctx(ctx);
-    if (!ctx->chan_set) throw ApiError(DSCE_ESTATE, "dsce_set_channel first");
-    if (ctx->nsnr <= 0) throw ApiError(DSCE_ESTATE, "dsce_set_snr first");
-    if (ctx->schemes.empty()) throw ApiError(DSCE_ESTATE, "no scheme added");
-    Scheme& s = get_scheme(ctx, id);
-    if (!out) throw ApiError(DSCE_EINVAL, "dsce_export: null out");
-    if (flags & ~(uint32_t)(DSCE_EXPORT_F32 | DSCE_EXPORT_DEVICE)) throw ApiError(DSCE_EINVAL, "dsce_export: unknown flag");
-    // fields in k_export's order
-    void* dst[6] = {out->y, out->hp_ls, out->h_est, out->h, out->xp, out->sym};
-    bool any = false;
-    for (void* p : dst) any = any || p;
-    if (!any) throw ApiError(DSCE_EINVAL, "dsce_export: no field requested");
-    if (out->h_est && !(s.mmse_ready && s.Wd))
-        throw ApiError(DSCE_ESTATE, "dsce_export: h_est needs dsce_build_mmse or dsce_set_interpolation");
+    Scheme& s = bulk_export_check(ctx, id, out, flags, DSCE_EXPORT_F32 | DSCE_EXPORT_DEVICE, "dsce_export");
     const bool f32 = (flags & DSCE_EXPORT_F32) != 0, to_device = (flags & DSCE_EXPORT_DEVICE) != 0;
-    if (to_device)
-        for (void* p : dst) {
-            if (!p) continue;
-            hipPointerAttribute_t at{};
-            const hipError_t e = hipPointerGetAttributes(&at, p);
-            if (e != hipSuccess) (void)hipGetLastError();
-            if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != ctx->device)
-                throw ApiError(DSCE_EINVAL, "dsce_export: DSCE_EXPORT_DEVICE with a pointer that is not device memory "
-                                            "of the context's GPU");
-        }
     const int LK = s.LK, NP = s.d.n_pilots, ND = s.d.n_data, nsnr = ctx->nsnr;
     const size_t csz = f32 ? sizeof(float2) : sizeof(double2);
-    // elements per realisation and element size of each field
-    const size_t per_rep[6] = {(size_t)nsnr * LK, (size_t)nsnr * NP, (size_t)nsnr * LK, (size_t)LK, (size_t)NP, (size_t)ND};
-    const size_t esz[6] = {csz, csz, csz, csz, csz, sizeof(int32_t)};
+    // fields in k_export's order: y, hp_ls and h_est per SNR point, h, xp and sym per realisation
     const int flen[6] = {LK, NP, LK, LK, NP, ND};
+    ExportSink sink{"dsce_export", 6, {out->y, out->hp_ls, out->h_est, out->h, out->xp, out->sym}, {},
+                    {csz, csz, csz, csz, csz, sizeof(int32_t)}, to_device};
+    for (int f = 0; f < 6; ++f) sink.per_rep[f] = (size_t)(f < 3 ? nsnr : 1) * flen[f];
+    sink.check(ctx, [&] {
+        if (out->h_est && !(s.mmse_ready && s.Wd))
+            throw ApiError(DSCE_ESTATE, "dsce_export: h_est needs dsce_build_mmse or dsce_set_interpolation");
+    });
     const int chunk = snr_chunk(ctx);
-    uint64_t done = 0;
-    while (done < n_rep) {
-        const uint64_t left = n_rep - done;
-        const int R = (int)std::min<uint64_t>((uint64_t)ctx->batch, (left + 63) / 64 * 64);
-        const int nvalid = (int)std::min<uint64_t>((uint64_t)R, left);
+    walk_batches(n_rep, ctx->batch, [&](uint64_t done, int R, int nvalid) {
         const uint64_t rep0 = first_rep + done;
         ensure_buffers(ctx, ctx->batch);
         McBuffers& b = ctx->buf;
@@ -2565,29 +2728,7 @@ int dsce_export(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, ui
         b.rvalid = nvalid;
         b.tr = nullptr;
         b.mse_err = b.mse_pow = nullptr;
-        ExportK ek{};
-        ek.row0 = to_device ? (long long)done : 0;
-        if (to_device) {
-            for (int f = 0; f < 6; ++f) ek.out[f] = dst[f];
-        } else {
-            // one batch of every requested field, each 256-byte aligned
-            size_t off[6], total = 0;
-            for (int f = 0; f < 6; ++f) {
-                off[f] = total;
-                if (dst[f]) total += ((size_t)nvalid * per_rep[f] * esz[f] + 255) / 256 * 256;
-            }
-            if (total > ctx->exp_stage_bytes) {
-                if (ctx->exp_stage) {
-                    DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-                    DSCE_HIP_CHECK(hipFree(ctx->exp_stage));
-                }
-                ctx->exp_stage = nullptr;
-                ctx->exp_stage_bytes = 0;
-                DSCE_HIP_CHECK(hipMalloc(&ctx->exp_stage, total));
-                ctx->exp_stage_bytes = total;
-            }
-            for (int f = 0; f < 6; ++f) ek.out[f] = dst[f] ? (char*)ctx->exp_stage + off[f] : nullptr;
-        }
+        sink.begin(ctx, done, nvalid);
         {
             Timed t(ctx, "k_jakes");
             if (ctx->jk_nsch != ctx->schemes.size()) update_jakes_chunks(ctx);
@@ -2600,6 +2741,9 @@ int dsce_export(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, ui
             launch_tx(ctx->stream, s.k, ctx->ch, s.d.bits_slot, s.d.pilot_slot, seed, rep0, b,
                       txrx_fft_ok(ctx->op, s.k, ctx->ch, b), ctx->op.tx_rows != 0);
         }
+        ExportK ek{};
+        ek.row0 = sink.row0;
+        for (int f = 0; f < 6; ++f) ek.out[f] = sink.out[f];
         ek.y = b.y;
         ek.h = b.h;
         ek.xp = b.xp;
@@ -2625,166 +2769,18 @@ int dsce_export(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, ui
             ek.snr0 = s0;
             // the per-realisation fields (h, xp, sym) go out with the first chunk
             for (int f = 0; f < 6; ++f)
-                ek.tiles[f] = dst[f] && (f < 3 || s0 == 0) ? (flen[f] + EXPORT_TILE - 1) / EXPORT_TILE : 0;
+                ek.tiles[f] = sink.dst[f] && (f < 3 || s0 == 0) ? (flen[f] + EXPORT_TILE - 1) / EXPORT_TILE : 0;
             {
                 Timed t(ctx, "k_export");
                 launch_export(ctx->stream, ek, f32);
             }
         }
         DSCE_HIP_CHECK(hipGetLastError());
-        if (!to_device)
-            for (int f = 0; f < 6; ++f)
-                if (dst[f])
-                    DSCE_HIP_CHECK(hipMemcpyAsync((char*)dst[f] + (size_t)done * per_rep[f] * esz[f], ek.out[f],
-                                                  (size_t)nvalid * per_rep[f] * esz[f], hipMemcpyDeviceToHost,
-                                                  ctx->stream));
-        done += (uint64_t)nvalid;
-    }
-    DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (ctx->timing) collect_timing(ctx);
+        sink.end(ctx, done, nvalid);
+    });
+    sink.finish(ctx);
     API_END
 }
-
-// The bulk exports behind run_batch (dsce_export_stages, dsce_export_llr): the
-// entry checks they share, and the loop over sub-batches.
-extern "C++" {
-namespace {
-struct BulkFields {
-    const char* what;           // the entry point's name, for messages
-    int n;                      // fields (<= 5)
-    void* dst[5];               // caller's destinations (null: not requested)
-    size_t per_rep[5];          // elements per realisation
-    size_t esz[5];              // bytes per element
-};
-
-Scheme& bulk_export_check(dsce_ctx* ctx, int32_t id, const void* out, uint32_t flags, uint32_t allowed,
-                          const char* what) {
-    const std::string w(what);
-    if (!ctx->chan_set) throw ApiError(DSCE_ESTATE, "dsce_set_channel first");
-    if (ctx->nsnr <= 0) throw ApiError(DSCE_ESTATE, "dsce_set_snr first");
-    if (ctx->schemes.empty()) throw ApiError(DSCE_ESTATE, "no scheme added");
-    Scheme& s = get_scheme(ctx, id);
-    if (!out) throw ApiError(DSCE_EINVAL, w + ": null out");
-    if (flags & ~allowed) throw ApiError(DSCE_EINVAL, w + ": unknown flag");
-    return s;
-}
-
-void bulk_fields_check(dsce_ctx* ctx, const Scheme& s, const BulkFields& f, bool to_device) {
-    const std::string w(f.what);
-    bool any = false;
-    for (int i = 0; i < f.n; ++i) any = any || f.dst[i];
-    if (!any) throw ApiError(DSCE_EINVAL, w + ": no field requested");
-    if (!(s.mmse_ready && s.Wd))
-        throw ApiError(DSCE_ESTATE, w + ": dsce_build_mmse first (or dsce_set_interpolation with n_iter 0)");
-    if (s.interp && ctx->niter > 0)
-        throw ApiError(DSCE_ESTATE, w + ": interference-cancellation iterations need the MMSE estimator "
-                                        "(n_iter must be 0 with an interpolation estimator)");
-    if (to_device)
-        for (int i = 0; i < f.n; ++i) {
-            if (!f.dst[i]) continue;
-            hipPointerAttribute_t at{};
-            const hipError_t e = hipPointerGetAttributes(&at, f.dst[i]);
-            if (e != hipSuccess) (void)hipGetLastError();
-            if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != ctx->device)
-                throw ApiError(DSCE_EINVAL, w + ": DSCE_EXPORT_DEVICE with a pointer that is not device "
-                                                "memory of the context's GPU");
-        }
-}
-
-// run_batch for scheme `id` with the stage kernels in TraceK's bulk mode (struct
-// Bulk), `launch` after each SNR chunk.  Scratch counters, no MSE sums,
-// Scheme::path restored.  A batch is cut into sub-batches of whole waves so that
-// the bulk arrays stay within option export_stage_mb (every realisation is its
-// own Philox streams: the cut does not show).  launch(bk, out, row0, R, nvalid,
-// snr0): the export kernel of the chunk that starts at SNR index snr0, from the
-// bulk arrays of bk into out[] (the caller's device memory, realisation 0 of the
-// sub-batch at row row0; or the staging buffer, at row 0).
-template <class Launch>
-void bulk_export(dsce_ctx* ctx, Scheme& s, int32_t id, uint64_t seed, uint64_t first_rep, uint64_t n_rep,
-                 bool to_device, const BulkFields& f, Launch launch) {
-    const int LK = s.LK, NP = s.d.n_pilots, ND = s.d.n_data, nsnr = ctx->nsnr, S = ctx->niter + 1;
-    // the bulk trace arrays of one unit: hP, diag(D_hat), y_ic and both decisions of every stage
-    const int chunk = snr_chunk(ctx);
-    const size_t unit_bytes = (size_t)S * (((size_t)NP + 2 * (size_t)LK) * sizeof(double2) + 2 * (size_t)ND * sizeof(int));
-    const size_t bound = (size_t)ctx->op.export_stage_mb << 20;
-    const size_t waves = std::max<size_t>(1, bound / (unit_bytes * 64 * (size_t)chunk));
-    const int rsub = (int)std::min<size_t>((size_t)(ctx->batch + 63) / 64, waves) * 64;
-    std::vector<void*> tmp;
-    auto talloc = [&](size_t bytes) {
-        void* p;
-        DSCE_HIP_CHECK(hipMalloc(&p, bytes));
-        tmp.push_back(p);
-        return p;
-    };
-    try {
-        Bulk bk;
-        bk.scheme = id;
-        bk.units = (size_t)rsub * chunk;
-        bk.k.LK = LK;
-        bk.k.ND = ND;
-        bk.k.unit = 0;
-        bk.k.yperf = nullptr;
-        bk.k.yest = (double2*)talloc(bk.units * S * LK * sizeof(double2));
-        bk.k.hest = (double2*)talloc(bk.units * S * LK * sizeof(double2));
-        bk.k.dec_e = (int*)talloc(bk.units * S * ND * sizeof(int));
-        bk.k.dec_p = (int*)talloc(bk.units * S * ND * sizeof(int));
-        bk.hp = (double2*)talloc(bk.units * S * NP * sizeof(double2));
-        bk.dev = (TraceK*)talloc(sizeof(TraceK));
-        const size_t ncount = ctx->schemes.size() * 4 * (size_t)nsnr * S;
-        bk.counters = (unsigned long long*)talloc(ncount * sizeof(unsigned long long));
-        DSCE_HIP_CHECK(hipMemsetAsync(bk.counters, 0, ncount * sizeof(unsigned long long), ctx->stream));
-        uint64_t done = 0;
-        while (done < n_rep) {
-            const uint64_t left = n_rep - done;
-            const int R = (int)std::min<uint64_t>((uint64_t)rsub, (left + 63) / 64 * 64);
-            const int nvalid = (int)std::min<uint64_t>((uint64_t)R, left);
-            ensure_buffers(ctx, ctx->batch);
-            ctx->buf.mse_err = ctx->buf.mse_pow = nullptr;
-            void* out[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-            const long long row0 = to_device ? (long long)done : 0;
-            if (to_device) {
-                for (int i = 0; i < f.n; ++i) out[i] = f.dst[i];
-            } else {
-                // one sub-batch of every requested field, each 256-byte aligned
-                size_t off[5], total = 0;
-                for (int i = 0; i < f.n; ++i) {
-                    off[i] = total;
-                    if (f.dst[i]) total += ((size_t)nvalid * f.per_rep[i] * f.esz[i] + 255) / 256 * 256;
-                }
-                if (total > ctx->exp_stage_bytes) {
-                    if (ctx->exp_stage) {
-                        DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-                        DSCE_HIP_CHECK(hipFree(ctx->exp_stage));
-                    }
-                    ctx->exp_stage = nullptr;
-                    ctx->exp_stage_bytes = 0;
-                    DSCE_HIP_CHECK(hipMalloc(&ctx->exp_stage, total));
-                    ctx->exp_stage_bytes = total;
-                }
-                for (int i = 0; i < f.n; ++i) out[i] = f.dst[i] ? (char*)ctx->exp_stage + off[i] : nullptr;
-            }
-            bk.flush = [&](int snr0) { launch(bk, out, row0, R, nvalid, snr0); };
-            run_batch(ctx, seed, first_rep + done, R, nvalid, nullptr, &bk);
-            if (!to_device)
-                for (int i = 0; i < f.n; ++i)
-                    if (f.dst[i])
-                        DSCE_HIP_CHECK(hipMemcpyAsync((char*)f.dst[i] + (size_t)done * f.per_rep[i] * f.esz[i], out[i],
-                                                      (size_t)nvalid * f.per_rep[i] * f.esz[i], hipMemcpyDeviceToHost,
-                                                      ctx->stream));
-            done += (uint64_t)nvalid;
-        }
-        DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        if (ctx->timing) collect_timing(ctx);
-    } catch (...) {
-        (void)hipStreamSynchronize(ctx->stream);
-        for (void* p : tmp) (void)hipFree(p);
-        throw;
-    }
-    for (void* p : tmp) DSCE_HIP_CHECK(hipFree(p));
-}
-
-}  // namespace
-}  // extern "C++"
 
 // Bulk per-stage export (ABI 10): bulk_export with k_export_stages after each SNR
 // chunk.  On a multi-device handle the handle itself is member 0.
@@ -2799,33 +2795,31 @@ int dsce_export_stages(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_
     const size_t csz = f32 ? sizeof(float2) : sizeof(double2);
     // fields in k_export_stages' order
     const int flen[5] = {NP, LK, LK, ND, ND};
-    BulkFields f{"dsce_export_stages", 5, {out->hp_ls, out->h_est, out->y_ic, out->dec_est, out->dec_perf}, {},
-                 {csz, csz, csz, sizeof(int32_t), sizeof(int32_t)}};
-    for (int i = 0; i < 5; ++i) f.per_rep[i] = (size_t)nsnr * S * flen[i];
-    bulk_fields_check(ctx, s, f, to_device);
-    bulk_export(ctx, s, id, seed, first_rep, n_rep, to_device, f,
-                [&](const Bulk& bk, void* const* dst, long long row0, int R, int nvalid, int snr0) {
-                    ExportStagesK ek{};
-                    ek.src[0] = bk.hp;
-                    ek.src[1] = bk.k.hest;
-                    ek.src[2] = bk.k.yest;
-                    ek.src[3] = bk.k.dec_e;
-                    ek.src[4] = bk.k.dec_p;
-                    for (int i = 0; i < 5; ++i) {
-                        ek.len[i] = flen[i];
-                        ek.tiles[i] = dst[i] ? (flen[i] + EXPORT_TILE - 1) / EXPORT_TILE : 0;
-                        ek.out[i] = dst[i];
-                    }
-                    ek.S = S;
-                    ek.R = R;
-                    ek.nsnr = nsnr;
-                    ek.rvalid = nvalid;
-                    ek.row0 = row0;
-                    ek.U = ctx->buf.U;
-                    ek.snr0 = snr0;
-                    Timed t(ctx, "k_export_stages");
-                    launch_export_stages(ctx->stream, ek, f32);
-                });
+    ExportSink sink{"dsce_export_stages", 5, {out->hp_ls, out->h_est, out->y_ic, out->dec_est, out->dec_perf}, {},
+                    {csz, csz, csz, sizeof(int32_t), sizeof(int32_t)}, to_device};
+    for (int i = 0; i < 5; ++i) sink.per_rep[i] = (size_t)nsnr * S * flen[i];
+    bulk_export(ctx, s, id, seed, first_rep, n_rep, sink, [&](const Bulk& bk, int snr0) {
+        ExportStagesK ek{};
+        ek.src[0] = bk.hp;
+        ek.src[1] = bk.k.hest;
+        ek.src[2] = bk.k.yest;
+        ek.src[3] = bk.k.dec_e;
+        ek.src[4] = bk.k.dec_p;
+        for (int i = 0; i < 5; ++i) {
+            ek.len[i] = flen[i];
+            ek.tiles[i] = sink.out[i] ? (flen[i] + EXPORT_TILE - 1) / EXPORT_TILE : 0;
+            ek.out[i] = sink.out[i];
+        }
+        ek.S = S;
+        ek.R = ctx->buf.R;
+        ek.nsnr = nsnr;
+        ek.rvalid = ctx->buf.rvalid;
+        ek.row0 = sink.row0;
+        ek.U = ctx->buf.U;
+        ek.snr0 = snr0;
+        Timed t(ctx, "k_export_stages");
+        launch_export_stages(ctx->stream, ek, f32);
+    });
     API_END
 }
 
@@ -2844,38 +2838,37 @@ int dsce_export_llr(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep
     const size_t rsz = f32 ? sizeof(float) : sizeof(double);
     const size_t per = (size_t)nsnr * S * ND;
     // fields in k_llr's order
-    BulkFields f{"dsce_export_llr", 3, {out->x_est, out->pn_eff, out->llr}, {per, per, per * m}, {2 * rsz, rsz, rsz}};
-    bulk_fields_check(ctx, s, f, to_device);
-    bulk_export(ctx, s, id, seed, first_rep, n_rep, to_device, f,
-                [&](const Bulk& bk, void* const* dst, long long row0, int R, int nvalid, int snr0) {
-                    LlrK a{};
-                    a.tab = s.llr;
-                    a.yic = bk.k.yest;
-                    a.hest = bk.k.hest;
-                    a.pn = ctx->d_pn;
-                    a.qn = s.qn;
-                    a.data_pos = s.k.data_pos;
-                    a.ph_ptr = s.k.ph_ptr;
-                    a.ph_col = s.k.ph_col;
-                    a.ph_val = s.k.ph_val;
-                    a.data_div = s.k.data_div;
-                    a.despread = s.k.despread;
-                    a.real_detect = s.k.real_detect;
-                    a.maxlog = (flags & DSCE_LLR_MAXLOG) ? 1 : 0;
-                    a.NP = s.k.NP;
-                    a.LK = s.LK;
-                    a.ND = ND;
-                    a.S = S;
-                    a.R = R;
-                    a.U = ctx->buf.U;
-                    a.snr0 = snr0;
-                    a.nsnr = nsnr;
-                    a.rvalid = nvalid;
-                    a.row0 = row0;
-                    for (int i = 0; i < 3; ++i) a.out[i] = dst[i];
-                    Timed t(ctx, "k_llr");
-                    launch_llr(ctx->stream, a, f32);
-                });
+    ExportSink sink{"dsce_export_llr", 3, {out->x_est, out->pn_eff, out->llr}, {per, per, per * m}, {2 * rsz, rsz, rsz},
+                    to_device};
+    bulk_export(ctx, s, id, seed, first_rep, n_rep, sink, [&](const Bulk& bk, int snr0) {
+        LlrK a{};
+        a.tab = s.llr;
+        a.yic = bk.k.yest;
+        a.hest = bk.k.hest;
+        a.pn = ctx->d_pn;
+        a.qn = s.qn;
+        a.data_pos = s.k.data_pos;
+        a.ph_ptr = s.k.ph_ptr;
+        a.ph_col = s.k.ph_col;
+        a.ph_val = s.k.ph_val;
+        a.data_div = s.k.data_div;
+        a.despread = s.k.despread;
+        a.real_detect = s.k.real_detect;
+        a.maxlog = (flags & DSCE_LLR_MAXLOG) ? 1 : 0;
+        a.NP = s.k.NP;
+        a.LK = s.LK;
+        a.ND = ND;
+        a.S = S;
+        a.R = ctx->buf.R;
+        a.U = ctx->buf.U;
+        a.snr0 = snr0;
+        a.nsnr = nsnr;
+        a.rvalid = ctx->buf.rvalid;
+        a.row0 = sink.row0;
+        for (int i = 0; i < 3; ++i) a.out[i] = sink.out[i];
+        Timed t(ctx, "k_llr");
+        launch_llr(ctx->stream, a, f32);
+    });
     API_END
 }
 
@@ -2890,29 +2883,16 @@ int dsce_llr_awgn(dsce_ctx* ctx, int32_t id, uint32_t flags, const double* x, co
     if (n > 0 && (!x || !pn || !llr_out)) throw ApiError(DSCE_EINVAL, "dsce_llr_awgn: null pointer");
     if (n > 0) {
         const int m = s.d.bits_per_symbol;
-        std::vector<void*> tmp;
-        auto talloc = [&](size_t bytes) {
-            void* p;
-            DSCE_HIP_CHECK(hipMalloc(&p, bytes));
-            tmp.push_back(p);
-            return p;
-        };
-        try {
-            double2* dx = (double2*)talloc((size_t)n * sizeof(double2));
-            double* dp = (double*)talloc((size_t)n_pn * sizeof(double));
-            double* dl = (double*)talloc((size_t)n * m * sizeof(double));
-            DSCE_HIP_CHECK(hipMemcpyAsync(dx, x, (size_t)n * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
-            DSCE_HIP_CHECK(hipMemcpyAsync(dp, pn, (size_t)n_pn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-            launch_llr_probe(ctx->stream, s.llr, dx, dp, n_pn, n, (flags & DSCE_LLR_MAXLOG) != 0, dl);
-            DSCE_HIP_CHECK(hipGetLastError());
-            DSCE_HIP_CHECK(hipMemcpyAsync(llr_out, dl, (size_t)n * m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-            DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        } catch (...) {
-            (void)hipStreamSynchronize(ctx->stream);
-            for (void* p : tmp) (void)hipFree(p);
-            throw;
-        }
-        for (void* p : tmp) DSCE_HIP_CHECK(hipFree(p));
+        DeviceTemps tmp(ctx);
+        double2* dx = tmp.alloc<double2>((size_t)n);
+        double* dp = tmp.alloc<double>((size_t)n_pn);
+        double* dl = tmp.alloc<double>((size_t)n * m);
+        DSCE_HIP_CHECK(hipMemcpyAsync(dx, x, (size_t)n * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
+        DSCE_HIP_CHECK(hipMemcpyAsync(dp, pn, (size_t)n_pn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        launch_llr_probe(ctx->stream, s.llr, dx, dp, n_pn, n, (flags & DSCE_LLR_MAXLOG) != 0, dl);
+        DSCE_HIP_CHECK(hipGetLastError());
+        DSCE_HIP_CHECK(hipMemcpyAsync(llr_out, dl, (size_t)n * m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        tmp.release_checked();
     }
     API_END
 }
@@ -2994,35 +2974,22 @@ int dsce_transmission_matrix(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t 
         qlo[c] = lo < hi ? lo : 0;
         qhi[c] = hi;
     }
-    std::vector<void*> tmp;
-    auto talloc = [&](size_t bytes) {
-        void* p;
-        DSCE_HIP_CHECK(hipMalloc(&p, bytes ? bytes : 1));
-        tmp.push_back(p);
-        return p;
-    };
-    try {
-        double2* ir = (double2*)talloc((size_t)ctx->ch.ntap * N * R * sizeof(double2));
-        double2* G = (double2*)talloc((size_t)N * LK * sizeof(double2));
-        double2* Q = (double2*)talloc((size_t)N * LK * sizeof(double2));
-        double2* hg = (double2*)talloc((size_t)N * LK * sizeof(double2));
-        double2* D = (double2*)talloc((size_t)LK * LK * sizeof(double2));
-        int* dq = (int*)talloc(2 * (size_t)LK * sizeof(int));
-        launch_jakes(ctx->stream, ctx->op, ctx->ch, seed, rep - (uint64_t)lane, R, ir);
-        DSCE_HIP_CHECK(hipMemcpyAsync(G, s.G.data(), s.G.size() * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
-        DSCE_HIP_CHECK(hipMemcpyAsync(Q, s.Q.data(), s.Q.size() * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
-        DSCE_HIP_CHECK(hipMemcpyAsync(dq, qlo.data(), LK * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        DSCE_HIP_CHECK(hipMemcpyAsync(dq + LK, qhi.data(), LK * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        setup_transmission_matrix(ctx->stream, ctx->ch, LK, ir, R, lane, G, Q, dq, dq + LK, hg, D);
-        DSCE_HIP_CHECK(hipGetLastError());
-        DSCE_HIP_CHECK(hipMemcpyAsync(d_out, D, (size_t)LK * LK * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
-        DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    } catch (...) {
-        (void)hipStreamSynchronize(ctx->stream);
-        for (void* p : tmp) (void)hipFree(p);
-        throw;
-    }
-    for (void* p : tmp) DSCE_HIP_CHECK(hipFree(p));
+    DeviceTemps tmp(ctx);
+    double2* ir = tmp.alloc<double2>((size_t)ctx->ch.ntap * N * R);
+    double2* G = tmp.alloc<double2>((size_t)N * LK);
+    double2* Q = tmp.alloc<double2>((size_t)N * LK);
+    double2* hg = tmp.alloc<double2>((size_t)N * LK);
+    double2* D = tmp.alloc<double2>((size_t)LK * LK);
+    int* dq = tmp.alloc<int>(2 * (size_t)LK);
+    launch_jakes(ctx->stream, ctx->op, ctx->ch, seed, rep - (uint64_t)lane, R, ir);
+    DSCE_HIP_CHECK(hipMemcpyAsync(G, s.G.data(), s.G.size() * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
+    DSCE_HIP_CHECK(hipMemcpyAsync(Q, s.Q.data(), s.Q.size() * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
+    DSCE_HIP_CHECK(hipMemcpyAsync(dq, qlo.data(), LK * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    DSCE_HIP_CHECK(hipMemcpyAsync(dq + LK, qhi.data(), LK * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    setup_transmission_matrix(ctx->stream, ctx->ch, LK, ir, R, lane, G, Q, dq, dq + LK, hg, D);
+    DSCE_HIP_CHECK(hipGetLastError());
+    DSCE_HIP_CHECK(hipMemcpyAsync(d_out, D, (size_t)LK * LK * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
+    tmp.release_checked();
     API_END
 }
 
@@ -3062,33 +3029,19 @@ int dsce_tx_matrices(dsce_ctx* ctx, const dsce_tx_desc* d, double* G_out, double
     t.phase0 = d->initial_phase;
     t.rx_scale = d->rx_scale;
     const size_t n = (size_t)t.N * t.L * t.K;
-    std::vector<void*> tmp;
-    try {
-        double* proto = nullptr;
-        if (t.kind == 1) {
-            DSCE_HIP_CHECK(hipMalloc((void**)&proto, t.proto * sizeof(double)));
-            tmp.push_back(proto);
-            DSCE_HIP_CHECK(hipMemcpy(proto, d->prototype, t.proto * sizeof(double), hipMemcpyHostToDevice));
-        }
-        double2 *G = nullptr, *Q = nullptr;
-        if (G_out) {
-            DSCE_HIP_CHECK(hipMalloc((void**)&G, n * sizeof(double2)));
-            tmp.push_back(G);
-        }
-        if (Q_out) {
-            DSCE_HIP_CHECK(hipMalloc((void**)&Q, n * sizeof(double2)));
-            tmp.push_back(Q);
-        }
-        setup_tx_matrix(ctx->stream, t, proto, G, Q);
-        DSCE_HIP_CHECK(hipGetLastError());
-        if (G_out) DSCE_HIP_CHECK(hipMemcpyAsync(G_out, G, n * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
-        if (Q_out) DSCE_HIP_CHECK(hipMemcpyAsync(Q_out, Q, n * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
-        DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    } catch (...) {
-        for (void* p : tmp) (void)hipFree(p);
-        throw;
+    DeviceTemps tmp(ctx);
+    double* proto = nullptr;
+    if (t.kind == 1) {
+        proto = tmp.alloc<double>(t.proto);
+        DSCE_HIP_CHECK(hipMemcpy(proto, d->prototype, t.proto * sizeof(double), hipMemcpyHostToDevice));
     }
-    for (void* p : tmp) DSCE_HIP_CHECK(hipFree(p));
+    double2* G = G_out ? tmp.alloc<double2>(n) : nullptr;
+    double2* Q = Q_out ? tmp.alloc<double2>(n) : nullptr;
+    setup_tx_matrix(ctx->stream, t, proto, G, Q);
+    DSCE_HIP_CHECK(hipGetLastError());
+    if (G_out) DSCE_HIP_CHECK(hipMemcpyAsync(G_out, G, n * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
+    if (Q_out) DSCE_HIP_CHECK(hipMemcpyAsync(Q_out, Q, n * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
+    tmp.release_checked();
     API_END
 }
 
@@ -3138,79 +3091,68 @@ int dsce_trace_unit_ex(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t rep, i
     ensure_buffers(ctx, ctx->batch);
     set_mse_buffers(ctx);
     const int LK = s.LK, ND = s.d.n_data, ns = ctx->niter + 1;
-    std::vector<void*> tmp;
-    auto talloc = [&](size_t bytes) {
-        void* p;
-        DSCE_HIP_CHECK(hipMalloc(&p, bytes));
-        tmp.push_back(p);
-        return p;
-    };
-    try {
-        Trace tr{id, k, 0, out};
-        tr.k.LK = LK;
-        tr.k.ND = ND;
-        tr.k.yest = (double2*)talloc((size_t)ns * LK * sizeof(double2));
-        tr.k.yperf = (double2*)talloc((size_t)ns * LK * sizeof(double2));
-        tr.k.hest = (double2*)talloc((size_t)ns * LK * sizeof(double2));
-        tr.k.dec_e = (int*)talloc((size_t)ns * ND * sizeof(int));
-        tr.k.dec_p = (int*)talloc((size_t)ns * ND * sizeof(int));
-        tr.dev = (TraceK*)talloc(sizeof(TraceK));
-        // all-ones bytes = NaN: "not written by any kernel" (0 is a legitimate value)
-        DSCE_HIP_CHECK(hipMemsetAsync(tr.k.yest, 0xff, (size_t)ns * LK * sizeof(double2), ctx->stream));
-        DSCE_HIP_CHECK(hipMemsetAsync(tr.k.yperf, 0xff, (size_t)ns * LK * sizeof(double2), ctx->stream));
-        DSCE_HIP_CHECK(hipMemsetAsync(tr.k.hest, 0xff, (size_t)ns * LK * sizeof(double2), ctx->stream));
-        // stages >= 1 of y_est / y_perf: NaN unless the host copies them from a
-        // per-unit buffer (unfused paths) or a kernel writes them (fused paths)
-        for (double* d : {out->yest_stages, out->yperf_stages})
-            if (d)
-                for (size_t i = 2 * (size_t)LK; i < 2 * (size_t)ns * LK; ++i) d[i] = std::nan("");
-        DSCE_HIP_CHECK(hipMemsetAsync(tr.k.dec_e, 0xff, (size_t)ns * ND * sizeof(int), ctx->stream));
-        DSCE_HIP_CHECK(hipMemsetAsync(tr.k.dec_p, 0xff, (size_t)ns * ND * sizeof(int), ctx->stream));
-        // the unit sits at lane 0 of a 64-realisation batch starting at rep
-        run_batch(ctx, seed, rep, 64, 64, &tr);
-        std::vector<double2> ye((size_t)ns * LK), yp((size_t)ns * LK);
-        DSCE_HIP_CHECK(hipMemcpyAsync(ye.data(), tr.k.yest, ye.size() * sizeof(double2), hipMemcpyDeviceToHost,
-                                      ctx->stream));
-        DSCE_HIP_CHECK(hipMemcpyAsync(yp.data(), tr.k.yperf, yp.size() * sizeof(double2), hipMemcpyDeviceToHost,
-                                      ctx->stream));
-        if (out->hest_stages)
-            DSCE_HIP_CHECK(hipMemcpyAsync(out->hest_stages, tr.k.hest, (size_t)ns * LK * sizeof(double2),
-                                          hipMemcpyDeviceToHost, ctx->stream));
-        if (out->dec_est)
-            DSCE_HIP_CHECK(hipMemcpyAsync(out->dec_est, tr.k.dec_e, (size_t)ns * ND * sizeof(int),
-                                          hipMemcpyDeviceToHost, ctx->stream));
-        if (out->dec_perf)
-            DSCE_HIP_CHECK(hipMemcpyAsync(out->dec_perf, tr.k.dec_p, (size_t)ns * ND * sizeof(int),
-                                          hipMemcpyDeviceToHost, ctx->stream));
-        DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        // stage 0 of y_est / y_perf is y itself; a row of a later stage is what a
-        // kernel wrote (NaN-initialised device trace), else what the host copied
-        // from y_est / y_perf (unfused paths), else NaN (not formed: e.g. pilot
-        // rows of the fused perfect-CSI chains)
-        auto merge = [&](double* dst, const std::vector<double2>& dev) {
-            if (!dst) return;
-            for (int st = 1; st < ns; ++st)
-                for (int r = 0; r < LK; ++r) {
-                    const double2 v = dev[(size_t)st * LK + r];
-                    double* d = dst + 2 * ((size_t)st * LK + r);
-                    if (!std::isnan(v.x)) {
-                        d[0] = v.x;
-                        d[1] = v.y;
-                    }
+    std::vector<double2> ye((size_t)ns * LK), yp((size_t)ns * LK);     // before tmp: they outlive its synchronise
+    DeviceTemps tmp(ctx);
+    Trace tr{id, k, 0, out};
+    tr.k.LK = LK;
+    tr.k.ND = ND;
+    tr.k.yest = tmp.alloc<double2>((size_t)ns * LK);
+    tr.k.yperf = tmp.alloc<double2>((size_t)ns * LK);
+    tr.k.hest = tmp.alloc<double2>((size_t)ns * LK);
+    tr.k.dec_e = tmp.alloc<int>((size_t)ns * ND);
+    tr.k.dec_p = tmp.alloc<int>((size_t)ns * ND);
+    tr.dev = tmp.alloc<TraceK>(1);
+    // all-ones bytes = NaN: "not written by any kernel" (0 is a legitimate value)
+    DSCE_HIP_CHECK(hipMemsetAsync(tr.k.yest, 0xff, (size_t)ns * LK * sizeof(double2), ctx->stream));
+    DSCE_HIP_CHECK(hipMemsetAsync(tr.k.yperf, 0xff, (size_t)ns * LK * sizeof(double2), ctx->stream));
+    DSCE_HIP_CHECK(hipMemsetAsync(tr.k.hest, 0xff, (size_t)ns * LK * sizeof(double2), ctx->stream));
+    // stages >= 1 of y_est / y_perf: NaN unless the host copies them from a
+    // per-unit buffer (unfused paths) or a kernel writes them (fused paths)
+    for (double* d : {out->yest_stages, out->yperf_stages})
+        if (d)
+            for (size_t i = 2 * (size_t)LK; i < 2 * (size_t)ns * LK; ++i) d[i] = std::nan("");
+    DSCE_HIP_CHECK(hipMemsetAsync(tr.k.dec_e, 0xff, (size_t)ns * ND * sizeof(int), ctx->stream));
+    DSCE_HIP_CHECK(hipMemsetAsync(tr.k.dec_p, 0xff, (size_t)ns * ND * sizeof(int), ctx->stream));
+    // the unit sits at lane 0 of a 64-realisation batch starting at rep
+    run_batch(ctx, seed, rep, 64, 64, &tr);
+    DSCE_HIP_CHECK(hipMemcpyAsync(ye.data(), tr.k.yest, ye.size() * sizeof(double2), hipMemcpyDeviceToHost,
+                                  ctx->stream));
+    DSCE_HIP_CHECK(hipMemcpyAsync(yp.data(), tr.k.yperf, yp.size() * sizeof(double2), hipMemcpyDeviceToHost,
+                                  ctx->stream));
+    if (out->hest_stages)
+        DSCE_HIP_CHECK(hipMemcpyAsync(out->hest_stages, tr.k.hest, (size_t)ns * LK * sizeof(double2),
+                                      hipMemcpyDeviceToHost, ctx->stream));
+    if (out->dec_est)
+        DSCE_HIP_CHECK(hipMemcpyAsync(out->dec_est, tr.k.dec_e, (size_t)ns * ND * sizeof(int),
+                                      hipMemcpyDeviceToHost, ctx->stream));
+    if (out->dec_perf)
+        DSCE_HIP_CHECK(hipMemcpyAsync(out->dec_perf, tr.k.dec_p, (size_t)ns * ND * sizeof(int),
+                                      hipMemcpyDeviceToHost, ctx->stream));
+    DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    // stage 0 of y_est / y_perf is y itself; a row of a later stage is what a
+    // kernel wrote (NaN-initialised device trace), else what the host copied
+    // from y_est / y_perf (unfused paths), else NaN (not formed: e.g. pilot
+    // rows of the fused perfect-CSI chains)
+    auto merge = [&](double* dst, const std::vector<double2>& dev) {
+        if (!dst) return;
+        for (int st = 1; st < ns; ++st)
+            for (int r = 0; r < LK; ++r) {
+                const double2 v = dev[(size_t)st * LK + r];
+                double* d = dst + 2 * ((size_t)st * LK + r);
+                if (!std::isnan(v.x)) {
+                    d[0] = v.x;
+                    d[1] = v.y;
                 }
-        };
-        merge(out->yest_stages, ye);
-        merge(out->yperf_stages, yp);
-        if (out->y) {
-            for (double* d : {out->yest_stages, out->yperf_stages})
-                if (d) memcpy(d, out->y, (size_t)LK * 2 * sizeof(double));
-        }
-        if (ctx->timing) collect_timing(ctx);
-    } catch (...) {
-        for (void* p : tmp) (void)hipFree(p);
-        throw;
+            }
+    };
+    merge(out->yest_stages, ye);
+    merge(out->yperf_stages, yp);
+    if (out->y) {
+        for (double* d : {out->yest_stages, out->yperf_stages})
+            if (d) memcpy(d, out->y, (size_t)LK * 2 * sizeof(double));
     }
-    for (void* p : tmp) DSCE_HIP_CHECK(hipFree(p));
+    if (ctx->timing) collect_timing(ctx);
+    tmp.release_checked();
     API_END
 }
 
@@ -3234,22 +3176,13 @@ int dsce_mmse_onetap(dsce_ctx* ctx, int32_t id, int32_t k, int32_t var, const do
     if (k < 0 || k >= ctx->nsnr || var < 0 || var > 1 || n <= 0 || !hp_ls || !h_out)
         throw ApiError(DSCE_EINVAL, "bad dsce_mmse_onetap arguments");
     const int NP = s.d.n_pilots, LK = s.LK;
-    double2* dh = nullptr;
-    double2* dp = nullptr;
-    DSCE_HIP_CHECK(hipMalloc(&dp, (size_t)NP * n * sizeof(double2)));
-    try {
-        DSCE_HIP_CHECK(hipMalloc(&dh, (size_t)LK * n * sizeof(double2)));
-        DSCE_HIP_CHECK(hipMemcpyAsync(dp, hp_ls, (size_t)NP * n * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
-        launch_mmse_onetap(ctx->stream, LK, NP, s.Wd + ((size_t)var * ctx->nsnr + k) * LK * NP, dp, n, dh);
-        DSCE_HIP_CHECK(hipMemcpyAsync(h_out, dh, (size_t)LK * n * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
-        DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    } catch (...) {
-        (void)hipFree(dp);
-        if (dh) (void)hipFree(dh);
-        throw;
-    }
-    DSCE_HIP_CHECK(hipFree(dp));
-    DSCE_HIP_CHECK(hipFree(dh));
+    DeviceTemps tmp(ctx);
+    double2* dp = tmp.alloc<double2>((size_t)NP * n);
+    double2* dh = tmp.alloc<double2>((size_t)LK * n);
+    DSCE_HIP_CHECK(hipMemcpyAsync(dp, hp_ls, (size_t)NP * n * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
+    launch_mmse_onetap(ctx->stream, LK, NP, s.Wd + ((size_t)var * ctx->nsnr + k) * LK * NP, dp, n, dh);
+    DSCE_HIP_CHECK(hipMemcpyAsync(h_out, dh, (size_t)LK * n * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
+    tmp.release_checked();
     API_END
 }
 

@@ -8,7 +8,9 @@ raise.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
+import functools
 import os
 
 import numpy as np
@@ -37,7 +39,6 @@ EXPORT_DEVICE = 1 << 1
 EXPORT_FIELDS = ("y", "hp_ls", "h_est", "h", "xp", "sym")
 # dsce_export_stages fields in the order of dsce_export_stages_out
 STAGE_FIELDS = ("hp_ls", "h_est", "y_ic", "dec_est", "dec_perf")
-_STAGE_INT = ("dec_est", "dec_perf")
 # dsce_llr_awgn / dsce_export_llr (include/dsce.h DSCE_LLR_MAXLOG; DSCE_HAS_LLR)
 LLR_MAXLOG = 1 << 2
 # dsce_export_llr fields in the order of dsce_export_llr_out
@@ -395,7 +396,38 @@ class Engine:
                     hest=v(bufs["hest"]).reshape(ns, LK), yest=v(bufs["yest"]).reshape(ns, LK),
                     yperf=v(bufs["yperf"]).reshape(ns, LK), dec_e=dec_e.reshape(ns, ND), dec_p=dec_p.reshape(ns, ND))
 
-    # -- bulk export (ABI 9) ---------------------------------------------------
+    # -- bulk exports: dsce_export (ABI 9), dsce_export_stages (ABI 10), dsce_export_llr (DSCE_HAS_LLR)
+    def _export_call(self, kind, sid, seed, first_rep, n_rep, flags, ptrs):
+        """The entry point of export `kind` (a key of _EXPORTS) on raw addresses:
+        ptrs maps a field to where its array starts (host, or device memory with
+        EXPORT_DEVICE in flags)."""
+        k = _EXPORTS[kind]
+        bad = [f for f in ptrs if f not in k.fields]
+        if bad:
+            raise ValueError("unknown %s field(s) %s (of %s)" % (k.noun, bad, list(k.fields)))
+        o = k.struct()
+        for f, p in ptrs.items():
+            setattr(o, f, C.cast(p, C.POINTER(C.c_int32)) if k.kinds[f] == "int32" else p)
+        self._chk(getattr(self.lib, k.entry)(self.h, int(sid), int(seed), int(first_rep), int(n_rep), int(flags),
+                                             C.byref(o)), k.entry)
+
+    # the raw-address form per kind, (sid, seed, first_rep, n_rep, flags, ptrs): what the
+    # GPU tests' guard-byte wrappers and tools/export_measure.py call
+    _export = functools.partialmethod(_export_call, "export")
+    _export_stages = functools.partialmethod(_export_call, "stages")
+    _export_llr = functools.partialmethod(_export_call, "llr")
+
+    def _bulk_export(self, kind, sid, seed, first_rep, n_rep, fields, arrays, method=None):
+        """Export `kind` into arrays that `arrays` (_HostArrays or _TorchArrays)
+        allocates: a dict field -> array."""
+        k = _EXPORTS[kind]
+        shapes = k.shapes(self, sid, n_rep)
+        out = {f: arrays.empty(shapes[f], k.kinds[f]) for f in fields}
+        arrays.ready()
+        flags = arrays.flags | (0 if method is None else self._llr_flag(method))
+        self._export_call(kind, sid, seed, first_rep, n_rep, flags, {f: arrays.address(a) for f, a in out.items()})
+        return out
+
     def export_shapes(self, sid, n_rep):
         """Shapes of dsce_export's arrays for n_rep realisations of scheme sid."""
         d = self.scheme_dims(sid)
@@ -403,30 +435,13 @@ class Engine:
         return dict(y=(n, d.n_snr, d.lk), hp_ls=(n, d.n_snr, d.n_pilots), h_est=(n, d.n_snr, d.lk), h=(n, d.lk),
                     xp=(n, d.n_pilots), sym=(n, d.n_data))
 
-    def _export(self, sid, seed, first_rep, n_rep, flags, ptrs):
-        bad = [f for f in ptrs if f not in EXPORT_FIELDS]
-        if bad:
-            raise ValueError("unknown export field(s) %s (of %s)" % (bad, list(EXPORT_FIELDS)))
-        o = ExportOut()
-        for f, p in ptrs.items():
-            setattr(o, f, C.cast(p, C.POINTER(C.c_int32)) if f == "sym" else p)
-        self._chk(self.lib.dsce_export(self.h, int(sid), int(seed), int(first_rep), int(n_rep), int(flags),
-                                       C.byref(o)), "dsce_export")
-
     def export(self, sid, seed, first_rep, n_rep, fields=EXPORT_FIELDS, dtype=np.complex128):
         """Per-realisation data of realisations [first_rep, first_rep + n_rep) of
         scheme sid (dsce_export) as a dict of NumPy arrays: y, hp_ls, h_est
         [n_rep][n_snr][LK | NP], h [n_rep][LK], xp [n_rep][NP] (dtype complex128,
         or complex64: DSCE_EXPORT_F32) and sym [n_rep][ND] int32.  Realisation
         rep is realisation rep of run() with the same seed."""
-        dt = np.dtype(dtype)
-        if dt not in (np.dtype(np.complex128), np.dtype(np.complex64)):
-            raise ValueError("export dtype must be complex128 or complex64")
-        shapes = self.export_shapes(sid, n_rep)
-        out = {f: np.zeros(shapes[f], dtype=np.int32 if f == "sym" else dt) for f in fields}
-        self._export(sid, seed, first_rep, n_rep, EXPORT_F32 if dt == np.dtype(np.complex64) else 0,
-                     {f: a.ctypes.data for f, a in out.items()})
-        return out
+        return self._bulk_export("export", sid, seed, first_rep, n_rep, fields, _HostArrays(dtype))
 
     def export_torch(self, sid, seed, first_rep, n_rep, fields=EXPORT_FIELDS, dtype=None, device=None):
         """export() into torch tensors on the context's GPU, written by the export
@@ -440,25 +455,9 @@ class Engine:
         (libdsce.so then binds to the runtime torch loaded, like bench.py and
         dsce.simulate under a launcher); the other order leaves torch without a
         usable device, which is reported here."""
-        import torch
-        dtype = torch.complex128 if dtype is None else dtype
-        if dtype not in (torch.complex128, torch.complex64):
-            raise ValueError("export_torch dtype must be torch.complex128 or torch.complex64")
-        if not torch.cuda.is_available():
-            raise DsceError("export_torch: torch sees no HIP device in this process; import torch before the "
-                            "first dsce.engine.Engine is created so that both use one HIP runtime")
-        if device is None:
-            device = self.group_info()[0][0]
-        shapes = self.export_shapes(sid, n_rep)
-        dev = "cuda:%d" % int(device)
-        out = {f: torch.empty(shapes[f], dtype=torch.int32 if f == "sym" else dtype, device=dev) for f in fields}
-        # the allocations (and any work torch queued on them) precede the engine's stream
-        torch.cuda.current_stream(dev).synchronize()
-        self._export(sid, seed, first_rep, n_rep, EXPORT_DEVICE | (EXPORT_F32 if dtype == torch.complex64 else 0),
-                     {f: t.data_ptr() for f, t in out.items()})
-        return out
+        return self._bulk_export("export", sid, seed, first_rep, n_rep, fields,
+                                 _TorchArrays(self, "export_torch", dtype, device))
 
-    # -- bulk per-stage export (ABI 10) ------------------------------------------
     def export_stages_shapes(self, sid, n_rep):
         """Shapes of dsce_export_stages' arrays for n_rep realisations of scheme sid
         (S = 1 + n_iter stages)."""
@@ -466,16 +465,6 @@ class Engine:
         n, S = int(n_rep), d.n_iter + 1
         return dict(hp_ls=(n, d.n_snr, S, d.n_pilots), h_est=(n, d.n_snr, S, d.lk), y_ic=(n, d.n_snr, S, d.lk),
                     dec_est=(n, d.n_snr, S, d.n_data), dec_perf=(n, d.n_snr, S, d.n_data))
-
-    def _export_stages(self, sid, seed, first_rep, n_rep, flags, ptrs):
-        bad = [f for f in ptrs if f not in STAGE_FIELDS]
-        if bad:
-            raise ValueError("unknown stage export field(s) %s (of %s)" % (bad, list(STAGE_FIELDS)))
-        o = ExportStagesOut()
-        for f, p in ptrs.items():
-            setattr(o, f, C.cast(p, C.POINTER(C.c_int32)) if f in _STAGE_INT else p)
-        self._chk(self.lib.dsce_export_stages(self.h, int(sid), int(seed), int(first_rep), int(n_rep), int(flags),
-                                              C.byref(o)), "dsce_export_stages")
 
     def export_stages(self, sid, seed, first_rep, n_rep, fields=STAGE_FIELDS, dtype=np.complex128):
         """Per-stage IC data of realisations [first_rep, first_rep + n_rep) of
@@ -487,36 +476,14 @@ class Engine:
         kernels of run() on its path; realisation rep is realisation rep of run()
         and of export() with the same seed.  NaN / -1: formed by no kernel of the
         path."""
-        dt = np.dtype(dtype)
-        if dt not in (np.dtype(np.complex128), np.dtype(np.complex64)):
-            raise ValueError("export dtype must be complex128 or complex64")
-        shapes = self.export_stages_shapes(sid, n_rep)
-        out = {f: np.zeros(shapes[f], dtype=np.int32 if f in _STAGE_INT else dt) for f in fields}
-        self._export_stages(sid, seed, first_rep, n_rep, EXPORT_F32 if dt == np.dtype(np.complex64) else 0,
-                            {f: a.ctypes.data for f, a in out.items()})
-        return out
+        return self._bulk_export("stages", sid, seed, first_rep, n_rep, fields, _HostArrays(dtype))
 
     def export_stages_torch(self, sid, seed, first_rep, n_rep, fields=STAGE_FIELDS, dtype=None, device=None):
         """export_stages() into torch tensors on the context's GPU, written by the
         export kernel itself (DSCE_EXPORT_DEVICE); see export_torch for dtype,
         device and the import order of torch and the engine."""
-        import torch
-        dtype = torch.complex128 if dtype is None else dtype
-        if dtype not in (torch.complex128, torch.complex64):
-            raise ValueError("export_stages_torch dtype must be torch.complex128 or torch.complex64")
-        if not torch.cuda.is_available():
-            raise DsceError("export_stages_torch: torch sees no HIP device in this process; import torch before the "
-                            "first dsce.engine.Engine is created so that both use one HIP runtime")
-        if device is None:
-            device = self.group_info()[0][0]
-        shapes = self.export_stages_shapes(sid, n_rep)
-        dev = "cuda:%d" % int(device)
-        out = {f: torch.empty(shapes[f], dtype=torch.int32 if f in _STAGE_INT else dtype, device=dev) for f in fields}
-        torch.cuda.current_stream(dev).synchronize()
-        self._export_stages(sid, seed, first_rep, n_rep,
-                            EXPORT_DEVICE | (EXPORT_F32 if dtype == torch.complex64 else 0),
-                            {f: t.data_ptr() for f, t in out.items()})
-        return out
+        return self._bulk_export("stages", sid, seed, first_rep, n_rep, fields,
+                                 _TorchArrays(self, "export_stages_torch", dtype, device))
 
     # -- soft outputs (DSCE_HAS_LLR) ----------------------------------------------
     @staticmethod
@@ -552,16 +519,6 @@ class Engine:
         base = (n, d.n_snr, S, d.n_data)
         return dict(x_est=base, pn_eff=base, llr=base + (self.llr_info(sid)["m"],))
 
-    def _export_llr(self, sid, seed, first_rep, n_rep, flags, ptrs):
-        bad = [f for f in ptrs if f not in LLR_FIELDS]
-        if bad:
-            raise ValueError("unknown LLR export field(s) %s (of %s)" % (bad, list(LLR_FIELDS)))
-        o = ExportLlrOut()
-        for f, p in ptrs.items():
-            setattr(o, f, p)
-        self._chk(self.lib.dsce_export_llr(self.h, int(sid), int(seed), int(first_rep), int(n_rep), int(flags),
-                                           C.byref(o)), "dsce_export_llr")
-
     def export_llr(self, sid, seed, first_rep, n_rep, fields=LLR_FIELDS, method="exact", dtype=np.complex128):
         """Soft outputs of the MMSE branch for realisations [first_rep, first_rep +
         n_rep) of scheme sid, every SNR point and stage (dsce_export_llr) as a dict
@@ -570,16 +527,7 @@ class Engine:
         shape, float64 / float32) and llr [n_rep][n_snr][S][ND][m], positive = bit
         1, method 'exact' (log-sum-exp) or 'maxlog'.  Realisation rep is
         realisation rep of run(), export() and export_stages() with the same seed."""
-        dt = np.dtype(dtype)
-        if dt not in (np.dtype(np.complex128), np.dtype(np.complex64)):
-            raise ValueError("export dtype must be complex128 or complex64")
-        f32 = dt == np.dtype(np.complex64)
-        rdt = np.dtype(np.float32 if f32 else np.float64)
-        shapes = self.export_llr_shapes(sid, n_rep)
-        out = {f: np.zeros(shapes[f], dtype=dt if f == "x_est" else rdt) for f in fields}
-        self._export_llr(sid, seed, first_rep, n_rep, self._llr_flag(method) | (EXPORT_F32 if f32 else 0),
-                         {f: a.ctypes.data for f, a in out.items()})
-        return out
+        return self._bulk_export("llr", sid, seed, first_rep, n_rep, fields, _HostArrays(dtype), method)
 
     def export_llr_torch(self, sid, seed, first_rep, n_rep, fields=LLR_FIELDS, method="exact", dtype=None,
                          device=None):
@@ -587,25 +535,8 @@ class Engine:
         kernel itself (DSCE_EXPORT_DEVICE); dtype torch.complex128 (x_est; pn_eff
         and llr float64) or torch.complex64 (float32).  See export_torch for
         device and the import order of torch and the engine."""
-        import torch
-        dtype = torch.complex128 if dtype is None else dtype
-        if dtype not in (torch.complex128, torch.complex64):
-            raise ValueError("export_llr_torch dtype must be torch.complex128 or torch.complex64")
-        if not torch.cuda.is_available():
-            raise DsceError("export_llr_torch: torch sees no HIP device in this process; import torch before the "
-                            "first dsce.engine.Engine is created so that both use one HIP runtime")
-        if device is None:
-            device = self.group_info()[0][0]
-        f32 = dtype == torch.complex64
-        rdt = torch.float32 if f32 else torch.float64
-        shapes = self.export_llr_shapes(sid, n_rep)
-        dev = "cuda:%d" % int(device)
-        out = {f: torch.empty(shapes[f], dtype=dtype if f == "x_est" else rdt, device=dev) for f in fields}
-        torch.cuda.current_stream(dev).synchronize()
-        self._export_llr(sid, seed, first_rep, n_rep,
-                         EXPORT_DEVICE | self._llr_flag(method) | (EXPORT_F32 if f32 else 0),
-                         {f: t.data_ptr() for f, t in out.items()})
-        return out
+        return self._bulk_export("llr", sid, seed, first_rep, n_rep, fields,
+                                 _TorchArrays(self, "export_llr_torch", dtype, device), method)
 
     # -- engine state ------------------------------------------------------------
     def scheme_dims(self, sid):
@@ -719,6 +650,76 @@ class Engine:
         wb = C.c_double()
         self._chk(self.lib.dsce_work_model(self.h, int(sid), C.byref(cm), C.byref(wb)), "dsce_work_model")
         return cm.value, wb.value
+
+
+# The bulk exports, one description each: the entry point, its ctypes struct, its
+# fields in the struct's order, each field's kind ("complex": complex128, or
+# complex64 with DSCE_EXPORT_F32; "real": float64 / float32; "int32"), what the
+# fields are called in a message, and shapes(engine, sid, n_rep).
+_ExportKind = collections.namedtuple("_ExportKind", "entry struct fields kinds noun shapes")
+_EXPORTS = {
+    "export": _ExportKind("dsce_export", ExportOut, EXPORT_FIELDS,
+                          dict(zip(EXPORT_FIELDS, ("complex",) * 5 + ("int32",))), "export", Engine.export_shapes),
+    "stages": _ExportKind("dsce_export_stages", ExportStagesOut, STAGE_FIELDS,
+                          dict(zip(STAGE_FIELDS, ("complex",) * 3 + ("int32",) * 2)), "stage export",
+                          Engine.export_stages_shapes),
+    "llr": _ExportKind("dsce_export_llr", ExportLlrOut, LLR_FIELDS,
+                       dict(zip(LLR_FIELDS, ("complex", "real", "real"))), "LLR export", Engine.export_llr_shapes),
+}
+
+
+class _HostArrays:
+    """NumPy arrays for Engine._bulk_export, complex fields of `dtype`."""
+
+    def __init__(self, dtype):
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.complex128), np.dtype(np.complex64)):
+            raise ValueError("export dtype must be complex128 or complex64")
+        f32 = dt == np.dtype(np.complex64)
+        self.flags = EXPORT_F32 if f32 else 0
+        self.types = {"complex": dt, "real": np.dtype(np.float32 if f32 else np.float64), "int32": np.int32}
+
+    def empty(self, shape, kind):
+        return np.zeros(shape, dtype=self.types[kind])
+
+    def ready(self):
+        pass
+
+    @staticmethod
+    def address(a):
+        return a.ctypes.data
+
+
+class _TorchArrays:
+    """torch tensors on the context's GPU for Engine._bulk_export (`what`: the
+    calling method, for messages), written in place (DSCE_EXPORT_DEVICE)."""
+
+    def __init__(self, eng, what, dtype, device):
+        import torch
+        dtype = torch.complex128 if dtype is None else dtype
+        if dtype not in (torch.complex128, torch.complex64):
+            raise ValueError("%s dtype must be torch.complex128 or torch.complex64" % what)
+        if not torch.cuda.is_available():
+            raise DsceError("%s: torch sees no HIP device in this process; import torch before the "
+                            "first dsce.engine.Engine is created so that both use one HIP runtime" % what)
+        if device is None:
+            device = eng.group_info()[0][0]
+        f32 = dtype == torch.complex64
+        self.torch = torch
+        self.dev = "cuda:%d" % int(device)
+        self.flags = EXPORT_DEVICE | (EXPORT_F32 if f32 else 0)
+        self.types = {"complex": dtype, "real": torch.float32 if f32 else torch.float64, "int32": torch.int32}
+
+    def empty(self, shape, kind):
+        return self.torch.empty(shape, dtype=self.types[kind], device=self.dev)
+
+    def ready(self):
+        # the allocations (and any work torch queued on them) precede the engine's stream
+        self.torch.cuda.current_stream(self.dev).synchronize()
+
+    @staticmethod
+    def address(t):
+        return t.data_ptr()
 
 
 def gpu_tx(device=0):

@@ -7,11 +7,16 @@
 // two-member multi-device context (member threads, host sum), and checks the
 // counts against the ones the regular library produced for the same inputs.
 // The error paths of the boundary (null outputs, unknown options, bad devices)
-// run too.  Exit status 0 = every check passed and ASAN reported nothing.
+// run too, and on the single-device context the calls that stage device memory
+// per call: the three bulk exports, dsce_llr_awgn and the single-unit trace.
+// Exit status 0 = every check passed and ASAN reported nothing.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <unistd.h>
+#include <algorithm>
+#include <cmath>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -88,7 +93,93 @@ void configure(dsce_ctx* ctx, const Setup& s, int32_t* sid) {
     check(dsce_set_batch(ctx, s.hdr[6]) == DSCE_OK, "set_batch", ctx);
 }
 
-void scenario(dsce_ctx* ctx, const Setup& s, const char* name) {
+// One bulk export with host destinations: the bytes per realisation of each
+// field, and the entry point on the fields' addresses.
+struct BulkCase {
+    const char* name;
+    std::vector<size_t> bytes;
+    std::function<int(char* const*, uint32_t)> call;       // (fields, flags)
+    size_t per_rep() const {
+        size_t t = 0;
+        for (size_t b : bytes) t += b;
+        return t;
+    }
+};
+
+// n realisations of the case into buf (field after field); returns the status
+int run_case(const BulkCase& c, size_t n, uint32_t flags, std::vector<char>& buf) {
+    buf.assign(c.per_rep() * n, 0);
+    std::vector<char*> f;
+    size_t off = 0;
+    for (size_t b : c.bytes) {
+        f.push_back(buf.data() + off);
+        off += b * n;
+    }
+    return c.call(f.data(), flags);
+}
+
+// The calls that stage device memory per call (the bulk exports, dsce_llr_awgn,
+// the single-unit trace): 70 realisations at batch 64 are two sub-batches with a
+// ragged tail; the exports run in the order of growing staging size, then the
+// smallest again (the staging buffer grows twice and is reused), each twice with
+// byte-identical output.  Sizes come from dsce_scheme_dims.
+void exports(dsce_ctx* ctx, const Setup& s, int32_t sid) {
+    dsce_dims d{};
+    int32_t llr_info[2] = {0, 0};
+    check(dsce_scheme_dims(ctx, sid, &d) == DSCE_OK, "scheme_dims", ctx);
+    check(dsce_llr_info(ctx, sid, llr_info) == DSCE_OK && llr_info[1] > 0, "llr_info", ctx);
+    check(dsce_set_batch(ctx, 64) == DSCE_OK, "set_batch(64)", ctx);
+    const size_t LK = (size_t)d.lk, NP = (size_t)d.n_pilots, ND = (size_t)d.n_data, nsnr = (size_t)d.n_snr,
+                 S = (size_t)d.n_iter + 1, m = (size_t)llr_info[1], cz = 2 * sizeof(double), n = 70;
+    const uint64_t seed = s.run[0], first = 5;
+    std::vector<BulkCase> cases = {
+        {"dsce_export", {nsnr * LK * cz, nsnr * NP * cz, nsnr * LK * cz, LK * cz, NP * cz, ND * sizeof(int32_t)},
+         [&](char* const* f, uint32_t flags) {
+             const dsce_export_out o{f[0], f[1], f[2], f[3], f[4], (int32_t*)f[5]};
+             return dsce_export(ctx, sid, seed, first, n, flags, &o);
+         }},
+        {"dsce_export_stages",
+         {nsnr * S * NP * cz, nsnr * S * LK * cz, nsnr * S * LK * cz, nsnr * S * ND * sizeof(int32_t),
+          nsnr * S * ND * sizeof(int32_t)},
+         [&](char* const* f, uint32_t flags) {
+             const dsce_export_stages_out o{f[0], f[1], f[2], (int32_t*)f[3], (int32_t*)f[4]};
+             return dsce_export_stages(ctx, sid, seed, first, n, flags, &o);
+         }},
+        {"dsce_export_llr", {nsnr * S * ND * cz, nsnr * S * ND * sizeof(double), nsnr * S * ND * m * sizeof(double)},
+         [&](char* const* f, uint32_t flags) {
+             const dsce_export_llr_out o{f[0], f[1], f[2]};
+             return dsce_export_llr(ctx, sid, seed, first, n, flags, &o);
+         }},
+    };
+    std::sort(cases.begin(), cases.end(), [](const BulkCase& a, const BulkCase& b) { return a.per_rep() < b.per_rep(); });
+    cases.push_back(cases[0]);
+    std::vector<char> a, b;
+    for (const BulkCase& c : cases) {
+        check(run_case(c, n, 0, a) == DSCE_OK, c.name, ctx);
+        check(run_case(c, n, 0, b) == DSCE_OK, c.name, ctx);
+        check(a == b, (std::string(c.name) + ": a repeat is byte-identical").c_str());
+    }
+    {
+        const double x[10] = {0.3, -0.2, 1.1, 0.9, -0.7, 0.1, 0.0, 0.0, 2.5, -2.5}, pn[5] = {0.1, 0.2, 0.05, 1.0, 0.3};
+        std::vector<double> llr(5 * m, 0.0);
+        check(dsce_llr_awgn(ctx, sid, 0, x, pn, 5, 5, llr.data()) == DSCE_OK && std::isfinite(llr[0]), "llr_awgn", ctx);
+    }
+    {
+        std::vector<double> y(2 * LK), h(2 * LK), hp(2 * S * NP), he(2 * S * LK), ye(2 * S * LK), yp(2 * S * LK);
+        std::vector<int32_t> de(S * ND), dp(S * ND);
+        const dsce_trace t{y.data(), h.data(), hp.data(), he.data(), ye.data(), yp.data(), de.data(), dp.data()};
+        check(dsce_trace_unit_ex(ctx, sid, seed, first, 0, &t) == DSCE_OK, "trace_unit_ex", ctx);
+    }
+    // a failing export: a host pointer passed as device memory is rejected, and
+    // the context runs on
+    check(run_case(cases[0], n, DSCE_EXPORT_DEVICE, a) == DSCE_EINVAL, "DSCE_EXPORT_DEVICE with a host pointer rejected");
+    check(dsce_set_batch(ctx, s.hdr[6]) == DSCE_OK, "set_batch", ctx);
+    std::vector<int64_t> counts(s.expect.size(), 0);
+    check(dsce_run(ctx, s.run[0], s.run[1], s.run[2], counts.data()) == DSCE_OK && counts == s.expect,
+          "run after the exports", ctx);
+}
+
+void scenario(dsce_ctx* ctx, const Setup& s, const char* name, bool with_exports) {
     int32_t sid = -1;
     configure(ctx, s, &sid);
     check(dsce_enable_mse(ctx, 1) == DSCE_OK, "enable_mse", ctx);
@@ -113,6 +204,7 @@ void scenario(dsce_ctx* ctx, const Setup& s, const char* name) {
     std::vector<int64_t> again(s.expect.size(), 0);
     check(dsce_run(ctx, s.run[0], s.run[1], s.run[2], again.data()) == DSCE_OK && again == s.expect,
           "run after errors", ctx);
+    if (with_exports) exports(ctx, s, sid);
     fprintf(stderr, "%s: done\n", name);
 }
 
@@ -166,7 +258,7 @@ int main(int argc, char** argv) {
     {
         dsce_ctx* ctx = nullptr;
         check(dsce_create(0, &ctx) == DSCE_OK && ctx, "create");
-        if (ctx) scenario(ctx, s, "single");
+        if (ctx) scenario(ctx, s, "single", true);
         check(dsce_destroy(ctx) == DSCE_OK, "destroy single");
     }
     {
@@ -178,7 +270,7 @@ int main(int argc, char** argv) {
             int32_t n = 0, devs[2] = {-1, -1}, reduce = -1;
             check(dsce_group_info(ctx, &n, devs, &reduce) == DSCE_OK && n == 2 && reduce == DSCE_REDUCE_HOST,
                   "group_info");
-            scenario(ctx, s, "multi");
+            scenario(ctx, s, "multi", false);
         }
         check(dsce_destroy(ctx) == DSCE_OK, "destroy multi");
     }
