@@ -1981,7 +1981,7 @@ struct ExportSink {
     // (asynchronous: finish() waits).
     void end(dsce_ctx* ctx, uint64_t done, int nvalid) const {
         for (int i = 0; !to_device && i < n; ++i)
-            if (dst[i])
+            if (dst[i] && bytes(i, nvalid))   // per_rep 0: a per-call output the entry point keeps itself (dsce_run_soft)
                 DSCE_HIP_CHECK(hipMemcpyAsync((char*)dst[i] + bytes(i, done), out[i], bytes(i, nvalid),
                                               hipMemcpyDeviceToHost, ctx->stream));
     }
@@ -2869,6 +2869,82 @@ int dsce_export_llr(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep
         Timed t(ctx, "k_llr");
         launch_llr(ctx->stream, a, f32);
     });
+    API_END
+}
+
+// BICM information loss (DSCE_HAS_SOFT_RUN): dsce_export_llr's run with
+// k_llr_info + k_llr_info_sum after each SNR chunk in place of k_llr: the LLRs are
+// turned into loss_b with the batch's own sidx and summed into device
+// accumulators that live for the call (declared before bulk_export's temporaries,
+// so they outlive its stream wait), then added into the caller's arrays once.
+// The sink's two fields carry no per-realisation data (per_rep 0): it checks that
+// one is requested and moves nothing.  b.h and b.sidx are the realisation's own at
+// flush time on every path of run_batch: the TX kernels write sidx once per batch,
+// k_txrx_fft / the diag(D) band pass write h (the former with the first chunk
+// only), and every later kernel takes both as const.
+int dsce_run_soft(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, uint64_t n_rep, uint32_t flags,
+                  const dsce_soft_out* out) {
+    TraceRange trace_range("dsce run soft");
+    API_BEGIN
+    check_ctx(ctx);
+    Scheme& s = bulk_export_check(ctx, id, out, flags, DSCE_LLR_MAXLOG, "dsce_run_soft");
+    const int ND = s.d.n_data, nsnr = ctx->nsnr, S = ctx->niter + 1;
+    ExportSink sink{"dsce_run_soft", 2, {out->loss_est, out->loss_perf0}, {0, 0}, {sizeof(double), sizeof(double)}, false};
+    const size_t n_est = out->loss_est ? (size_t)nsnr * S * 2 : 0, n_perf = out->loss_perf0 ? (size_t)nsnr * 2 : 0;
+    LlrInfoK q{};
+    q.st_lo = out->loss_est ? 0 : S;
+    q.nst = (out->loss_est ? S : 0) + (out->loss_perf0 ? 1 : 0);
+    std::vector<double> host(n_est + n_perf);
+    DeviceTemps tmp(ctx);
+    if (q.nst > 0) {
+        // no field requested: bulk_export refuses below, before anything is launched
+        double* acc = tmp.alloc<double>(n_est + n_perf);
+        DSCE_HIP_CHECK(hipMemsetAsync(acc, 0, (n_est + n_perf) * sizeof(double), ctx->stream));
+        q.acc_est = out->loss_est ? acc : nullptr;
+        q.acc_perf = out->loss_perf0 ? acc + n_est : nullptr;
+        const int rmax = (ctx->batch + 63) / 64 * 64;
+        q.part = tmp.alloc<double>(llr_info_parts(ND, rmax, snr_chunk(ctx), q.nst));
+    }
+    bulk_export(ctx, s, id, seed, first_rep, n_rep, sink, [&](const Bulk& bk, int snr0) {
+        LlrK& a = q.k;
+        a.tab = s.llr;
+        a.yic = bk.k.yest;
+        a.hest = bk.k.hest;
+        a.pn = ctx->d_pn;
+        a.qn = s.qn;
+        a.data_pos = s.k.data_pos;
+        a.ph_ptr = s.k.ph_ptr;
+        a.ph_col = s.k.ph_col;
+        a.ph_val = s.k.ph_val;
+        a.data_div = s.k.data_div;
+        a.despread = s.k.despread;
+        a.real_detect = s.k.real_detect;
+        a.maxlog = (flags & DSCE_LLR_MAXLOG) ? 1 : 0;
+        a.NP = s.k.NP;
+        a.LK = s.LK;
+        a.ND = ND;
+        a.S = S;
+        a.R = ctx->buf.R;
+        a.U = ctx->buf.U;
+        a.snr0 = snr0;
+        a.nsnr = nsnr;
+        a.rvalid = ctx->buf.rvalid;
+        q.h = ctx->buf.h;
+        q.sidx = ctx->buf.sidx;
+        q.considered = s.k.considered;
+        if (a.R > (ctx->batch + 63) / 64 * 64 || a.U / a.R > snr_chunk(ctx))
+            throw ApiError(DSCE_EINVAL, "dsce_run_soft: partial sums too small");
+        Timed t(ctx, "k_llr_info");
+        launch_llr_info(ctx->stream, q);
+    });
+    if (n_rep > 0 && !host.empty()) {
+        DSCE_HIP_CHECK(hipMemcpyAsync(host.data(), q.acc_est ? q.acc_est : q.acc_perf, host.size() * sizeof(double),
+                                      hipMemcpyDeviceToHost, ctx->stream));
+        DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        for (size_t i = 0; i < n_est; ++i) out->loss_est[i] += host[i];
+        for (size_t i = 0; i < n_perf; ++i) out->loss_perf0[i] += host[n_est + i];
+    }
+    tmp.release_checked();
     API_END
 }
 

@@ -344,6 +344,34 @@ struct LlrK {
     void* out[3];             // null: not requested
 };
 void launch_llr(hipStream_t s, const LlrK& a, bool f32);
+// BICM information loss of one batch and SNR chunk after its last stage
+// (k_llr_info + k_llr_info_sum; dsce_run_soft): k_llr's x_est / pn_eff / LLRs of
+// every stage, each LLR turned into loss_b = log2(1 + exp(-(2 t_b - 1) LLR_b))
+// with the transmitted bit t_b and summed instead of stored.  k: k_llr's
+// arguments (out and row0 unused).  Stage index S is the perfect-CSI one-tap
+// receiver: y = stage 0 of yic, the channel from h[l][rep] instead of hest.
+// One block = 64 units x one tile of LLR_INFO_LT data symbols of one stage; it
+// writes its pair of sums (all symbols, considered symbols) to slot
+// ((sc nst + st) nb + wave ntile + tile) of `part`, sc the SNR index in the
+// chunk, st = stage - st_lo, wave = (unit % R) / 64, nb = (R / 64) ntile.
+// k_llr_info_sum then adds each (sc, st)'s nb slots, in slot order, into
+// acc_est[snr][stage][2] / acc_perf[snr][2].  No atomics: the sums of two
+// identical calls are bit-identical.
+constexpr int LLR_INFO_LT = 64;
+struct LlrInfoK {
+    LlrK k;
+    const double2* h;         // [LK][R] perfect-CSI diag(D) of the batch
+    const uint16_t* sidx;     // [ND][R] transmitted symbol indices
+    const int* considered;    // ND no-edge flags
+    int st_lo, nst;           // stages [st_lo, st_lo + nst) of 0 .. S (S = the perfect-CSI one-tap receiver)
+    double* part;             // [chunk SNR points][nst][nb][2] scratch
+    double* acc_est;          // [nsnr][S][2], or null
+    double* acc_perf;         // [nsnr][2], or null
+};
+inline size_t llr_info_parts(int ND, int R, int nchunk, int nst) {
+    return (size_t)nchunk * nst * (R / 64) * ((ND + LLR_INFO_LT - 1) / LLR_INFO_LT) * 2;
+}
+void launch_llr_info(hipStream_t s, const LlrInfoK& a);
 // LLRs of n points x (pn: one value or one per point), out [n][m]
 void launch_llr_probe(hipStream_t s, const LlrTab& t, const double2* x, const double* pn, long long n_pn, long long n,
                       bool maxlog, double* out);

@@ -1,7 +1,9 @@
 // kernels_llr.hip — soft outputs: SignalConstellation.LLR_AWGN
 // (SignalConstellation.m:103-122) as defined in include/dsce.h, for single points
 // (k_llr_probe; dsce_llr_awgn) and in bulk for every stage of the MMSE branch
-// (k_llr; dsce_export_llr).  One device function, llr_demap, serves both.
+// (k_llr; dsce_export_llr), and the BICM information loss summed from those LLRs
+// on the device (k_llr_info + k_llr_info_sum; dsce_run_soft).  One device
+// function, llr_demap, serves all of them.
 //
 //   LLR_b(x, pn) = log sum_{bit_b = 1} exp(-e_i) - log sum_{bit_b = 0} exp(-e_i),   e_i = |x - s_i|^2 / pn
 //
@@ -277,6 +279,116 @@ void launch_llr(hipStream_t s, const LlrK& a, bool f32) {
     if (!a.out[0] && !a.out[1] && !a.out[2]) return;
     if (a.tab.m <= 4) launch_llr_lt<16>(s, a, f32);
     else launch_llr_lt<8>(s, a, f32);
+}
+
+// loss_b ln 2 = log(1 + exp(-z)), z = (2 t_b - 1) LLR_b, in the stable form of
+// include/dsce.h: finite for every finite LLR, NaN for NaN (fmax drops it, exp keeps it)
+__device__ __forceinline__ double info_loss_nats(double llr, bool bit) {
+    const double z = bit ? llr : -llr;
+    return fmax(-z, 0.0) + log1p(exp(-fabs(z)));
+}
+
+// k_llr_info — k_llr with a sum in place of the stores.  Phase 1 is k_llr's,
+// statement for statement (lane = unit, wave w the tile's symbols w, w + 4, ..),
+// with the channel of pseudo-stage S read from h[l][rep]; the store callback
+// adds the bit's loss, in nats, to the lane's two fp64 sums (all symbols,
+// considered symbols) with the transmitted index sidx[j][rep], contiguous across
+// the wave.  No transpose, so no LDS tile: LLR_INFO_LT symbols per block.  The
+// block's lanes are summed by a fixed butterfly per wave and in wave order
+// through LDS, divided by ln 2 once, and go to the block's own slot of `part`.
+__global__ void __launch_bounds__(256) k_llr_info(LlrInfoK q) {
+    __shared__ double red[4][2];
+    constexpr int LT = LLR_INFO_LT;
+    const LlrK& a = q.k;
+    const int ntile = (a.ND + LT - 1) / LT;
+    const int st = blockIdx.y / ntile, tile = blockIdx.y % ntile, e0 = tile * LT;
+    const int stage = q.st_lo + st;
+    const bool perf = stage == a.S;                        // the perfect-CSI one-tap receiver
+    const int first = blockIdx.x * 64;                     // first unit of the block (one SNR point: R % 64 == 0)
+    const int sc = first / a.R, snr = a.snr0 + sc;
+    const int rl0 = first % a.R;
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int rep = rl0 + lane;
+    const bool counts = rep < a.rvalid;                    // a padding realisation adds nothing
+    const size_t U = (size_t)a.U, unit = (size_t)first + lane;
+    const size_t base = perf ? 0 : (size_t)stage * a.LK;   // perfect CSI: y = stage 0 of y_ic
+    const double2* hsrc = perf ? q.h : a.hest;
+    const size_t hU = perf ? (size_t)a.R : U, hunit = perf ? (size_t)rep : unit;
+    const double pnk = a.pn[snr];
+    double sum_all = 0.0, sum_con = 0.0;
+    if (rl0 < a.rvalid)                                    // else a wave of tail padding (block-uniform)
+        for (int e = w; e < LT; e += 4) {
+            const int j = e0 + e;
+            if (j >= a.ND) break;                          // wave-uniform
+            double2 x;
+            double pe;
+            if (a.despread) {                              // x = P^H (y ./ h), row NP + j of P^H
+                double2 acc = make_double2(0.0, 0.0);
+                double pacc = 0.0;
+                const int j0 = a.ph_ptr[a.NP + j], j1 = a.ph_ptr[a.NP + j + 1];
+                for (int jj = j0; jj < j1; ++jj) {
+                    const int l = a.ph_col[jj];
+                    const double2 pv = a.ph_val[jj];
+                    const double2 y = a.yic[(base + l) * U + unit], h = hsrc[(base + l) * hU + hunit];
+                    c_fma(acc, pv, c_div(y, h));
+                    pacc += (pv.x * pv.x + pv.y * pv.y) * (pnk * a.qn[l]) / (h.x * h.x + h.y * h.y);
+                }
+                x = make_double2(acc.x / a.data_div, acc.y / a.data_div);
+                pe = pacc / (a.data_div * a.data_div);
+            } else {
+                const int l = a.data_pos[j];
+                const double2 y = a.yic[(base + l) * U + unit], h = hsrc[(base + l) * hU + hunit];
+                const double2 qt = c_div(y, h);
+                x = make_double2(qt.x / a.data_div, qt.y / a.data_div);
+                pe = pnk * a.qn[l] / ((h.x * h.x + h.y * h.y) * (a.data_div * a.data_div));
+            }
+            if (a.real_detect) x.y = 0.0;
+            const unsigned t = q.sidx[(size_t)j * a.R + rep];
+            double sym = 0.0;
+            llr_demap(a.tab, x, pe, a.maxlog != 0, [&](int b, double v) { sym += info_loss_nats(v, (t >> b) & 1); });
+            if (counts) {
+                sum_all += sym;
+                if (q.considered[j]) sum_con += sym;
+            }
+        }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        sum_all += __shfl_xor(sum_all, d, 64);
+        sum_con += __shfl_xor(sum_con, d, 64);
+    }
+    if (lane == 0) {
+        red[w][0] = sum_all;
+        red[w][1] = sum_con;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        const int nb = (a.R / 64) * ntile;
+        const size_t slot = ((size_t)(sc * q.nst + st) * nb + (size_t)(rl0 / 64) * ntile + tile);
+        const int k = threadIdx.x;
+        q.part[slot * 2 + k] = (((red[0][k] + red[1][k]) + red[2][k]) + red[3][k]) / M_LN2;
+    }
+}
+
+// one thread per (SNR point of the chunk, stage, edge class): its nb slots in slot order
+__global__ void __launch_bounds__(64) k_llr_info_sum(LlrInfoK q, int nb, int n) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const int k = i & 1, st = (i >> 1) % q.nst, sc = (i >> 1) / q.nst;
+    const double* p = q.part + (size_t)(i >> 1) * nb * 2 + k;
+    double s = 0.0;
+    for (int b = 0; b < nb; ++b) s += p[2 * b];
+    const int stage = q.st_lo + st, snr = q.k.snr0 + sc;
+    double* dst = stage < q.k.S ? q.acc_est + ((size_t)snr * q.k.S + stage) * 2 + k : q.acc_perf + (size_t)snr * 2 + k;
+    *dst += s;
+}
+
+void launch_llr_info(hipStream_t s, const LlrInfoK& a) {
+    if (a.nst <= 0) return;
+    const int ntile = (a.k.ND + LLR_INFO_LT - 1) / LLR_INFO_LT;
+    hipLaunchKernelGGL(k_llr_info, dim3(a.k.U / 64, a.nst * ntile), dim3(256), 0, s, a);
+    const int n = (a.k.U / a.k.R) * a.nst * 2;
+    hipLaunchKernelGGL(k_llr_info_sum, dim3((n + 63) / 64), dim3(64), 0, s, a, (a.k.R / 64) * ntile, n);
 }
 
 }  // namespace dsce

@@ -27,7 +27,7 @@ EXPORTED = [
     "dsce_scheme_dims", "dsce_path_info", "dsce_set_option", "dsce_get_option", "dsce_fp64_mfma_peak",
     "dsce_kernel_work", "dsce_structured_check", "dsce_create_multi", "dsce_group_info",
     "dsce_transmission_matrix", "dsce_jakes_info", "dsce_export", "dsce_export_stages",
-    "dsce_llr_awgn", "dsce_export_llr", "dsce_llr_info",
+    "dsce_llr_awgn", "dsce_export_llr", "dsce_llr_info", "dsce_run_soft",
 ]
 
 ABI_VERSION = 10
@@ -104,6 +104,10 @@ class ExportLlrOut(C.Structure):
     _fields_ = [("x_est", C.c_void_p), ("pn_eff", C.c_void_p), ("llr", C.c_void_p)]
 
 
+class SoftOut(C.Structure):
+    _fields_ = [("loss_est", C.POINTER(C.c_double)), ("loss_perf0", C.POINTER(C.c_double))]
+
+
 class TxDesc(C.Structure):
     _fields_ = [("kind", C.c_int32), ("n_subcarriers", C.c_int32), ("n_symbols", C.c_int32),
                 ("n_samples", C.c_int32), ("fft_size", C.c_int32), ("intermediate_bin", C.c_int32),
@@ -174,6 +178,7 @@ def load_library(path=None):
     lib.dsce_export_llr.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
                                     C.POINTER(ExportLlrOut)]
     lib.dsce_llr_info.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32)]
+    lib.dsce_run_soft.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(SoftOut)]
     for name in EXPORTED:
         fn = getattr(lib, name)
         if name != "dsce_last_error":
@@ -537,6 +542,48 @@ class Engine:
         device and the import order of torch and the engine."""
         return self._bulk_export("llr", sid, seed, first_rep, n_rep, fields,
                                  _TorchArrays(self, "export_llr_torch", dtype, device), method)
+
+    # -- BICM rate from the LLRs (DSCE_HAS_SOFT_RUN) --------------------------------
+    def soft_shapes(self, sid):
+        """Shapes of dsce_run_soft's arrays for scheme sid."""
+        d = self.scheme_dims(sid)
+        return dict(loss_est=(d.n_snr, d.n_iter + 1, 2), loss_perf0=(d.n_snr, 2))
+
+    def run_soft(self, sid, seed, first_rep, n_rep, method="exact", out=None):
+        """Information loss of the LLRs that export_llr would return for realisations
+        [first_rep, first_rep + n_rep) of scheme sid, summed on the GPU
+        (dsce_run_soft): dict of float64 arrays loss_est [n_snr][S][2] (MMSE branch,
+        per stage; last axis 0 = all data symbols, 1 = the considered ones) and
+        loss_perf0 [n_snr][2] (perfect-CSI one-tap receiver), in bits, summed over
+        the realisations, the data symbols and their m bits (see
+        dsce.modulation.bicm_info_loss).  The sums are ADDED into the arrays of
+        `out` (a dict with either or both keys, C-contiguous float64; only the
+        given ones are computed) and `out` is returned; without it both are
+        computed from zero.  bicm_rate turns a sum into a rate."""
+        shapes = self.soft_shapes(sid)
+        if out is None:
+            out = {f: np.zeros(shp) for f, shp in shapes.items()}
+        o = SoftOut()
+        for f, a in out.items():
+            if f not in shapes:
+                raise ValueError("unknown soft output %r (of %s)" % (f, list(shapes)))
+            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous
+                    and a.shape == shapes[f]):
+                raise ValueError("%s must be a C-contiguous float64 array of shape %s" % (f, shapes[f]))
+            setattr(o, f, _dptr(a))
+        self._chk(self.lib.dsce_run_soft(self.h, int(sid), int(seed), int(first_rep), int(n_rep),
+                                         self._llr_flag(method), C.byref(o)), "dsce_run_soft")
+        return out
+
+    def bicm_rate(self, sid, loss, n_rep):
+        """I = m - loss / (n_rep ND_edge) bits per data symbol for sums `loss` of
+        run_soft over n_rep realisations (last axis: the edge classes of
+        bits_per_rep).  Exact LLRs: the BICM mutual-information estimate; max-log:
+        the mismatched-decoder rate at scaling 1, a lower bound that may be
+        negative."""
+        m = self.llr_info(sid)["m"]
+        nd = self.bits_per_rep(sid).astype(np.float64) / m
+        return m - np.asarray(loss, dtype=np.float64) / (float(n_rep) * nd)
 
     # -- engine state ------------------------------------------------------------
     def scheme_dims(self, sid):

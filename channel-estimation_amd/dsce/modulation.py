@@ -421,3 +421,21 @@ def llr_awgn(symbols, bitmap, y, Pn, method="exact"):
                 out[a:a + 16384, b] = ((m0 - m1) + np.log(np.exp(-(e1 - m1)).sum(axis=1, keepdims=True))
                                        - np.log(np.exp(-(e0 - m0)).sum(axis=1, keepdims=True)))[:, 0]
     return out
+
+
+def bicm_info_loss(llr, bits):
+    """Information loss per bit, in bits, of LLRs `llr` (positive = bit 1, any
+    shape) against the transmitted bits `bits` (0 / 1 or bool, broadcast against
+    llr):
+
+        loss = log2(1 + exp(-z)),   z = (2 bit - 1) llr,
+
+    evaluated as (max(-z, 0) + log1p(exp(-|z|))) / ln 2: finite for every finite
+    LLR, NaN for NaN, 1 at llr = 0, -> 0 for a confident correct bit, about
+    |llr| / ln 2 for a confident wrong one.  The BICM rate of m-bit symbols is
+    m - (mean loss per symbol); with max-log LLRs the same expression is the rate
+    of the mismatched decoder at scaling 1 (a lower bound, possibly negative).
+    The definition that dsce_run_soft (include/dsce.h) sums on the GPU."""
+    llr = np.asarray(llr, dtype=float)
+    z = np.where(np.asarray(bits).astype(bool), llr, -llr)
+    return (np.maximum(-z, 0.0) + np.log1p(np.exp(-np.abs(z)))) / np.log(2.0)

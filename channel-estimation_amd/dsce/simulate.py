@@ -61,9 +61,20 @@ def main(argv=None):
     ap.add_argument("--stop-after", type=int, default=None,
                     help="process at most this many realisations (per rank) in this invocation, then leave "
                          "the checkpoint for --resume (needs --checkpoint)")
+    ap.add_argument("--rate", choices=("exact", "maxlog"), default=None,
+                    help="also the BICM rate per scheme, SNR point and IC stage from the demapper's LLRs "
+                         "(exact, or max-log: the mismatched-decoder rate), summed on the GPU (dsce_run_soft)")
     a = ap.parse_args(argv)
     if (a.resume or a.stop_after is not None) and not a.checkpoint:
         raise SystemExit("--resume / --stop-after need --checkpoint")
+    if a.rate:
+        # the rate pass is one plain sweep of the rank's realisations after the counters
+        for on, what in ((a.checkpoint, "--checkpoint (the rate sums are not checkpointed)"),
+                         (a.shard == "snr", "--shard snr (the rate pass runs every SNR point of the engine)"),
+                         (a.devices, "--devices (dsce_run_soft is member 0's on a multi-device context)"),
+                         (a.config == "doubly_flat", "--config doubly_flat (its own simulator)")):
+            if on:
+                raise SystemExit("--rate cannot be combined with " + what)
 
     from dsce import results
     from dsce.configs import build_setup
@@ -112,7 +123,9 @@ def main(argv=None):
     counts = np.zeros((len(names), 2, 2, nsnr, nst), dtype=np.int64)
     err = np.zeros((len(names), nsnr, nst))
     pw = np.zeros((len(names), nsnr))
-    bits = None
+    loss_e = np.zeros((len(names), nsnr, nst, 2))
+    loss_p = np.zeros((len(names), nsnr, 2))
+    bits, rate_s = None, 0.0
     setup_s, t0 = 0.0, time.perf_counter()
     ck_path = None
     if a.checkpoint:
@@ -160,6 +173,14 @@ def main(argv=None):
             e_, p_ = eng.mse()
             err[:, s0:s0 + ns, :] = e0 + e_
             pw[:, s0:s0 + ns] = p0 + p_
+        if a.rate:
+            # one dsce_run_soft pass per scheme over the same realisations, in steps of the batch
+            t1 = time.perf_counter()
+            for i in range(len(names)):
+                out = {"loss_est": loss_e[i], "loss_perf0": loss_p[i]}
+                for at in range(0, mine, step):
+                    eng.run_soft(i, a.seed, first + at, min(step, mine - at), a.rate, out)
+            rate_s = time.perf_counter() - t1
         eng.close()
     complete = done >= mine
     if distributed:
@@ -179,7 +200,11 @@ def main(argv=None):
         if distributed:
             dist.destroy_process_group()
         return 0
-    extra = {"setup_s": setup_s, "seconds": prior_s + time.perf_counter() - t0, "ranks": world, "shard": a.shard}
+    # "seconds" is the counter loop's: the rate pass is timed on its own
+    extra = {"setup_s": setup_s, "seconds": prior_s + time.perf_counter() - t0 - rate_s, "ranks": world,
+             "shard": a.shard}
+    if a.rate:
+        extra["bicm_rate_seconds"] = rate_s
     if ck_path and a.resume:
         extra["resumed"] = True
     if devices:
@@ -192,6 +217,9 @@ def main(argv=None):
         if a.mse:
             err = allreduce_counts(err, dev)
             pw = allreduce_counts(pw, dev)
+        if a.rate:
+            loss_e = allreduce_counts(loss_e, dev)
+            loss_p = allreduce_counts(loss_p, dev)
         # bits per realisation are a property of the schemes: every rank with work
         # has them (collective on every rank, so a rank with an empty shard too)
         have = np.array([0 if bits is None else 1], dtype=np.int64)
@@ -208,6 +236,17 @@ def main(argv=None):
         extra["seconds"] = float(t.item())
     if a.mse:
         extra["nmse"] = {s: (err[i] / pw[i][:, None]).tolist() for i, s in enumerate(names)}
+    if a.rate:
+        # I = m - loss / (n_rep ND_edge) bits per data symbol (include/dsce.h), both edge classes
+        from dsce.results import EDGE
+        extra["bicm_rate"] = {}
+        for i, s in enumerate(names):
+            m = S.schemes[s].bits_per_symbol
+            nd = np.asarray(bits[i], dtype=np.float64) / m
+            extra["bicm_rate"][s] = {
+                "mmse": {e: (m - loss_e[i, :, :, k] / (reps * nd[k])).tolist() for k, e in enumerate(EDGE)},
+                "perfect_onetap": {e: (m - loss_p[i, :, k] / (reps * nd[k])).tolist() for k, e in enumerate(EDGE)},
+                "method": a.rate}
     extra["realisations_per_s"] = reps / extra["seconds"]
     res = results.make(S, names, counts, bits, reps, a.seed, extra=extra)
     if rank != 0:
@@ -225,6 +264,12 @@ def main(argv=None):
                    "ber_ic_mmse": float(res["ber"][s]["mmse"]["all"][k][-1]),
                    "ber_onetap_mmse": float(res["ber"][s]["mmse"]["all"][k][0])} for s in names}
     print(json.dumps(summary))
+    if a.rate:
+        print(json.dumps({s: {"snr_db": float(S.snr_db[k]), "method": a.rate,
+                              "bicm_rate_ic_mmse": r["mmse"]["all"][k][-1],
+                              "bicm_rate_onetap_mmse": r["mmse"]["all"][k][0],
+                              "bicm_rate_onetap_perfect": r["perfect_onetap"]["all"][k]}
+                          for s, r in extra["bicm_rate"].items()}))
     if distributed:
         dist.destroy_process_group()
     return 0

@@ -39,6 +39,8 @@
  *   dsce_llr_awgn         <- SignalConstellation.LLR_AWGN        SignalConstellation.m:103-122
  *   dsce_export_llr       <- the same applied to the demapper input of every stage
  *                            of the MMSE branch                  script:429-444, :519-525
+ *   dsce_run_soft         <- no counterpart in the script: the BICM rate of those LLRs
+ *                            against the BITS stream, summed per SNR point and stage
  *
  * Conventions
  *  - Return 0 on success, a negative DSCE_E* code on failure; the message is
@@ -86,6 +88,8 @@
  * data of every realisation in bulk.  Every ABI 9 entry point is unchanged.
  * DSCE_HAS_LLR (still ABI 10: purely additive) announces dsce_llr_awgn,
  * dsce_export_llr and dsce_llr_info: soft outputs of the demapper.
+ * DSCE_HAS_SOFT_RUN (still ABI 10) announces dsce_run_soft: the BICM information
+ * loss of those LLRs, summed on the device.
  */
 #ifndef DSCE_H
 #define DSCE_H
@@ -515,6 +519,54 @@ int dsce_export_llr(dsce_ctx* ctx, int32_t scheme_id, uint64_t seed, uint64_t fi
  * the LLR is a PAM LLR over that axis' levels; every Gray map of the reference),
  * 0 the full-table form over all M symbols; out2[1] = m. */
 int dsce_llr_info(dsce_ctx* ctx, int32_t scheme_id, int32_t* out2);
+
+/* ---- BICM rate from the LLRs (DSCE_HAS_SOFT_RUN; additive, ABI 10) -------- */
+/* Definitions (x_est, pn_eff, LLR_b exact or max-log, the symbol table and the
+ * bit convention are those of the soft-output section above).
+ *  t_b(rep, j) = bit b of the transmitted symbol index of data symbol j: the sym
+ *  of dsce_export.  The information loss of one bit, in bits,
+ *    loss_b = log2(1 + exp(-(2 t_b - 1) LLR_b)),
+ *  is evaluated as (max(-z, 0) + log1p(exp(-|z|))) / ln 2, z = (2 t_b - 1) LLR_b:
+ *  finite for every finite LLR, NaN for NaN, 1 at LLR = 0, -> 0 for a confident
+ *  correct bit, about |LLR| / ln 2 for a confident wrong one.  (The engine sums
+ *  the numerators and divides by ln 2 once per block of 64 realisations.)
+ *  loss_est[snr][stage][edge]: the sum of loss_b over the realisations of the
+ *  call, the data symbols j of the edge class (0 = all, 1 = considered[j]) and the
+ *  m bits, with the LLRs of the MMSE branch at that stage: exactly what
+ *  dsce_export_llr exports.  [n_snr][1 + n_iter][2] doubles, C order.
+ *  loss_perf0[snr][edge]: the same sum for the perfect-CSI one-tap receiver:
+ *  x_est and pn_eff formed as for stage 0 with h (diag(D), the h of dsce_export)
+ *  in place of h_est.  [n_snr][2] doubles.  The perfect-CSI IC stages have no
+ *  such figure: the bulk mode does not stage y_perf.
+ *  Rate: I = m - loss / (n_rep ND_edge) bits per data symbol, ND_edge m from
+ *  dsce_bits_per_rep.  With the exact LLRs this is the estimate of the BICM
+ *  mutual information of the demapper output (the achievable rate of
+ *  bit-interleaved coded modulation under the AWGN model of LLR_AWGN).  With
+ *  DSCE_LLR_MAXLOG it is the rate of the mismatched decoder at LLR scaling 1: a
+ *  lower bound on what a decoder can get from those LLRs, and it may be negative.
+ *  pn_eff holds the AWGN only: where residual interference dominates (high SNR
+ *  before cancellation) the exact LLRs are overconfident too, and their figure is
+ *  then likewise a mismatched-decoder rate that can be negative. */
+#define DSCE_HAS_SOFT_RUN 1
+typedef struct {          /* each optional */
+    double* loss_est;     /* [n_snr][1 + n_iter][2] */
+    double* loss_perf0;   /* [n_snr][2]             */
+} dsce_soft_out;
+
+/* ADDS the sums defined above into the caller's host arrays, as dsce_run adds
+ * into err_counts.  The run is dsce_export_llr's (realisation `rep` is
+ * realisation `rep` of dsce_run with the same seed; batches, SNR chunks, the
+ * export_stage_mb cut, padding realisations that contribute nothing, any
+ * n_rep >= 0 with n_rep = 0 adding nothing, no change to the error counters, the
+ * MSE sums or dsce_path_info), with "k_llr_info" (its name under
+ * dsce_enable_timing) after each SNR chunk: the LLRs are reduced on the device,
+ * in a fixed order without atomics, so two identical calls return identical
+ * bits; a few doubles reach the host once per call.  flags: 0 | DSCE_LLR_MAXLOG;
+ * any other bit (DSCE_EXPORT_F32 and DSCE_EXPORT_DEVICE too) is DSCE_EINVAL, as
+ * are a null out and no field requested.  DSCE_ESTATE as for dsce_export_llr.
+ * On a multi-device handle the call is member 0's. */
+int dsce_run_soft(dsce_ctx* ctx, int32_t scheme_id, uint64_t seed, uint64_t first_rep, uint64_t n_rep,
+                  uint32_t flags, const dsce_soft_out* out);
 
 /* ---- engine state ------------------------------------------------------- */
 int dsce_scheme_dims(dsce_ctx* ctx, int32_t scheme_id, dsce_dims* dims);
