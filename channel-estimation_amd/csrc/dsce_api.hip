@@ -156,6 +156,11 @@ struct Scheme {
     // soft demapper (dsce_llr_awgn, dsce_export_llr): its tables, and ||Q[:, l]||^2 per row l (device)
     LlrTab llr{};
     double* qn = nullptr;
+    // dsce_set_llr_scale: pn_eff <- g pn_eff in dsce_export_llr / dsce_run_soft (device; null: not installed),
+    // [nsnr][S][ND] for the MMSE stages and [nsnr][ND] for the perfect-CSI one-tap receiver, with host copies
+    double* g_est = nullptr;
+    double* g_perf0 = nullptr;
+    std::vector<double> g_est_host, g_perf0_host;
 };
 
 }  // namespace dsce
@@ -2433,6 +2438,14 @@ int dsce_set_channel(dsce_ctx* ctx, const dsce_channel_desc* d) {
     return fanout(ctx, [&](dsce_ctx* c) { return set_channel_one(c, d); });
 }
 
+static void drop_llr_scale(dsce_ctx* ctx, Scheme& s) {
+    if (s.g_est) free_alloc(ctx, s.g_est);
+    if (s.g_perf0) free_alloc(ctx, s.g_perf0);
+    s.g_est = s.g_perf0 = nullptr;
+    s.g_est_host.clear();
+    s.g_perf0_host.clear();
+}
+
 static int set_snr_one(dsce_ctx* ctx, const double* pn_time, int32_t n_snr, int32_t n_iter) {
     API_BEGIN
     check_ctx(ctx);
@@ -2446,6 +2459,7 @@ static int set_snr_one(dsce_ctx* ctx, const double* pn_time, int32_t n_snr, int3
     for (auto& s : ctx->schemes) {
         s->mmse_ready = false;
         if (s->interp) upload_interp(ctx, *s);
+        drop_llr_scale(ctx, *s);                           // their shape was the previous arguments
     }
     const size_t n = ctx->schemes.size() * 4 * (size_t)n_snr * (n_iter + 1);
     ctx->counters_n = 0;
@@ -2823,6 +2837,35 @@ int dsce_export_stages(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_
     API_END
 }
 
+// k_llr's arguments for the sub-batch in ctx->buf and the SNR chunk that starts
+// at snr0 (out, row0 and scale are the entry point's)
+static LlrK llr_args(dsce_ctx* ctx, const Scheme& s, const Bulk& bk, int snr0, bool maxlog) {
+    LlrK a{};
+    a.tab = s.llr;
+    a.yic = bk.k.yest;
+    a.hest = bk.k.hest;
+    a.pn = ctx->d_pn;
+    a.qn = s.qn;
+    a.data_pos = s.k.data_pos;
+    a.ph_ptr = s.k.ph_ptr;
+    a.ph_col = s.k.ph_col;
+    a.ph_val = s.k.ph_val;
+    a.data_div = s.k.data_div;
+    a.despread = s.k.despread;
+    a.real_detect = s.k.real_detect;
+    a.maxlog = maxlog ? 1 : 0;
+    a.NP = s.k.NP;
+    a.LK = s.LK;
+    a.ND = s.d.n_data;
+    a.S = ctx->niter + 1;
+    a.R = ctx->buf.R;
+    a.U = ctx->buf.U;
+    a.snr0 = snr0;
+    a.nsnr = ctx->nsnr;
+    a.rvalid = ctx->buf.rvalid;
+    return a;
+}
+
 // Bulk soft outputs (DSCE_HAS_LLR): bulk_export with k_llr after each SNR chunk:
 // x_est, pn_eff and the LLRs of every stage of the MMSE branch from the bulk
 // arrays y_ic / h_est.  On a multi-device handle the handle itself is member 0.
@@ -2841,29 +2884,8 @@ int dsce_export_llr(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep
     ExportSink sink{"dsce_export_llr", 3, {out->x_est, out->pn_eff, out->llr}, {per, per, per * m}, {2 * rsz, rsz, rsz},
                     to_device};
     bulk_export(ctx, s, id, seed, first_rep, n_rep, sink, [&](const Bulk& bk, int snr0) {
-        LlrK a{};
-        a.tab = s.llr;
-        a.yic = bk.k.yest;
-        a.hest = bk.k.hest;
-        a.pn = ctx->d_pn;
-        a.qn = s.qn;
-        a.data_pos = s.k.data_pos;
-        a.ph_ptr = s.k.ph_ptr;
-        a.ph_col = s.k.ph_col;
-        a.ph_val = s.k.ph_val;
-        a.data_div = s.k.data_div;
-        a.despread = s.k.despread;
-        a.real_detect = s.k.real_detect;
-        a.maxlog = (flags & DSCE_LLR_MAXLOG) ? 1 : 0;
-        a.NP = s.k.NP;
-        a.LK = s.LK;
-        a.ND = ND;
-        a.S = S;
-        a.R = ctx->buf.R;
-        a.U = ctx->buf.U;
-        a.snr0 = snr0;
-        a.nsnr = nsnr;
-        a.rvalid = ctx->buf.rvalid;
+        LlrK a = llr_args(ctx, s, bk, snr0, (flags & DSCE_LLR_MAXLOG) != 0);
+        a.scale = s.g_est;
         a.row0 = sink.row0;
         for (int i = 0; i < 3; ++i) a.out[i] = sink.out[i];
         Timed t(ctx, "k_llr");
@@ -2907,28 +2929,9 @@ int dsce_run_soft(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, 
     }
     bulk_export(ctx, s, id, seed, first_rep, n_rep, sink, [&](const Bulk& bk, int snr0) {
         LlrK& a = q.k;
-        a.tab = s.llr;
-        a.yic = bk.k.yest;
-        a.hest = bk.k.hest;
-        a.pn = ctx->d_pn;
-        a.qn = s.qn;
-        a.data_pos = s.k.data_pos;
-        a.ph_ptr = s.k.ph_ptr;
-        a.ph_col = s.k.ph_col;
-        a.ph_val = s.k.ph_val;
-        a.data_div = s.k.data_div;
-        a.despread = s.k.despread;
-        a.real_detect = s.k.real_detect;
-        a.maxlog = (flags & DSCE_LLR_MAXLOG) ? 1 : 0;
-        a.NP = s.k.NP;
-        a.LK = s.LK;
-        a.ND = ND;
-        a.S = S;
-        a.R = ctx->buf.R;
-        a.U = ctx->buf.U;
-        a.snr0 = snr0;
-        a.nsnr = nsnr;
-        a.rvalid = ctx->buf.rvalid;
+        a = llr_args(ctx, s, bk, snr0, (flags & DSCE_LLR_MAXLOG) != 0);
+        a.scale = s.g_est;
+        q.scale_perf = s.g_perf0;
         q.h = ctx->buf.h;
         q.sidx = ctx->buf.sidx;
         q.considered = s.k.considered;
@@ -2945,6 +2948,96 @@ int dsce_run_soft(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, 
         for (size_t i = 0; i < n_perf; ++i) out->loss_perf0[i] += host[n_est + i];
     }
     tmp.release_checked();
+    API_END
+}
+
+// Demapper noise ratio (DSCE_HAS_LLR_SCALE): dsce_run_soft's run with k_llr_calib
+// after each SNR chunk: per (SNR point, stage, data symbol) the sum over the
+// realisations of c |x_est - s_t|^2 / pn_eff against the unscaled AWGN pn_eff
+// (installed tables are not read).  The device accumulators live for the call
+// (declared before bulk_export's temporaries, so they outlive its stream wait)
+// and are added into the caller's arrays once.
+int dsce_run_calib(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, uint64_t n_rep, uint32_t flags,
+                   const dsce_calib_out* out) {
+    TraceRange trace_range("dsce run calib");
+    API_BEGIN
+    check_ctx(ctx);
+    Scheme& s = bulk_export_check(ctx, id, out, flags, 0, "dsce_run_calib");
+    const int ND = s.d.n_data, nsnr = ctx->nsnr, S = ctx->niter + 1;
+    ExportSink sink{"dsce_run_calib", 2, {out->ratio_est, out->ratio_perf0}, {0, 0}, {sizeof(double), sizeof(double)},
+                    false};
+    const size_t n_est = out->ratio_est ? (size_t)nsnr * S * ND : 0, n_perf = out->ratio_perf0 ? (size_t)nsnr * ND : 0;
+    LlrCalibK q{};
+    q.st_lo = out->ratio_est ? 0 : S;
+    q.nst = (out->ratio_est ? S : 0) + (out->ratio_perf0 ? 1 : 0);
+    std::vector<double> host(n_est + n_perf);
+    DeviceTemps tmp(ctx);
+    if (q.nst > 0) {
+        // no field requested: bulk_export refuses below, before anything is launched
+        double* acc = tmp.alloc<double>(n_est + n_perf);
+        DSCE_HIP_CHECK(hipMemsetAsync(acc, 0, (n_est + n_perf) * sizeof(double), ctx->stream));
+        q.acc_est = out->ratio_est ? acc : nullptr;
+        q.acc_perf = out->ratio_perf0 ? acc + n_est : nullptr;
+    }
+    bulk_export(ctx, s, id, seed, first_rep, n_rep, sink, [&](const Bulk& bk, int snr0) {
+        q.k = llr_args(ctx, s, bk, snr0, false);
+        q.h = ctx->buf.h;
+        q.sidx = ctx->buf.sidx;
+        Timed t(ctx, "k_llr_calib");
+        launch_llr_calib(ctx->stream, q);
+    });
+    if (n_rep > 0 && !host.empty()) {
+        DSCE_HIP_CHECK(hipMemcpyAsync(host.data(), q.acc_est ? q.acc_est : q.acc_perf, host.size() * sizeof(double),
+                                      hipMemcpyDeviceToHost, ctx->stream));
+        DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        for (size_t i = 0; i < n_est; ++i) out->ratio_est[i] += host[i];
+        for (size_t i = 0; i < n_perf; ++i) out->ratio_perf0[i] += host[n_est + i];
+    }
+    tmp.release_checked();
+    API_END
+}
+
+static int set_llr_scale_one(dsce_ctx* ctx, int32_t id, const double* g_est, const double* g_perf0) {
+    API_BEGIN
+    check_ctx(ctx);
+    if (ctx->nsnr <= 0) throw ApiError(DSCE_ESTATE, "dsce_set_snr first");
+    Scheme& s = get_scheme(ctx, id);
+    const size_t n_perf = (size_t)ctx->nsnr * s.d.n_data, n_est = n_perf * (ctx->niter + 1);
+    // both tables are checked before either changes
+    for (int t = 0; t < 2; ++t) {
+        const double* g = t ? g_perf0 : g_est;
+        for (size_t i = 0; g && i < (t ? n_perf : n_est); ++i)
+            if (!(std::isfinite(g[i]) && g[i] > 0.0))
+                throw ApiError(DSCE_EINVAL, "dsce_set_llr_scale: every entry must be finite and > 0");
+    }
+    drop_llr_scale(ctx, s);
+    if (g_est) {
+        s.g_est_host.assign(g_est, g_est + n_est);
+        s.g_est = dupload(ctx, s.g_est_host);
+    }
+    if (g_perf0) {
+        s.g_perf0_host.assign(g_perf0, g_perf0 + n_perf);
+        s.g_perf0 = dupload(ctx, s.g_perf0_host);
+    }
+    API_END
+}
+
+int dsce_set_llr_scale(dsce_ctx* ctx, int32_t id, const double* g_est, const double* g_perf0) {
+    return fanout(ctx, [&](dsce_ctx* c) { return set_llr_scale_one(c, id, g_est, g_perf0); });
+}
+
+int dsce_get_llr_scale(dsce_ctx* ctx, int32_t id, double* g_est, double* g_perf0, int32_t* set2) {
+    API_BEGIN
+    check_ctx(ctx);
+    if (ctx->nsnr <= 0) throw ApiError(DSCE_ESTATE, "dsce_set_snr first");
+    Scheme& s = get_scheme(ctx, id);
+    const size_t n_perf = (size_t)ctx->nsnr * s.d.n_data, n_est = n_perf * (ctx->niter + 1);
+    if (set2) {
+        set2[0] = s.g_est ? 1 : 0;
+        set2[1] = s.g_perf0 ? 1 : 0;
+    }
+    for (size_t i = 0; g_est && i < n_est; ++i) g_est[i] = s.g_est ? s.g_est_host[i] : 1.0;
+    for (size_t i = 0; g_perf0 && i < n_perf; ++i) g_perf0[i] = s.g_perf0 ? s.g_perf0_host[i] : 1.0;
     API_END
 }
 

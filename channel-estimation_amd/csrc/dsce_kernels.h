@@ -342,6 +342,7 @@ struct LlrK {
     int NP, LK, ND, S, R, U, snr0, nsnr, rvalid;
     long long row0;
     void* out[3];             // null: not requested
+    const double* scale;      // [nsnr][S][ND] pn_eff <- scale pn_eff (dsce_set_llr_scale), or null
 };
 void launch_llr(hipStream_t s, const LlrK& a, bool f32);
 // BICM information loss of one batch and SNR chunk after its last stage
@@ -367,11 +368,34 @@ struct LlrInfoK {
     double* part;             // [chunk SNR points][nst][nb][2] scratch
     double* acc_est;          // [nsnr][S][2], or null
     double* acc_perf;         // [nsnr][2], or null
+    const double* scale_perf; // [nsnr][ND] the scale of pseudo-stage S, or null
 };
 inline size_t llr_info_parts(int ND, int R, int nchunk, int nst) {
     return (size_t)nchunk * nst * (R / 64) * ((ND + LLR_INFO_LT - 1) / LLR_INFO_LT) * 2;
 }
 void launch_llr_info(hipStream_t s, const LlrInfoK& a);
+// Demapper noise ratio of one batch and SNR chunk after its last stage
+// (k_llr_calib; dsce_run_calib): k_llr_info's x_est / pn_eff of stages
+// [st_lo, st_lo + nst) (stage S = the perfect-CSI one-tap receiver), and per data
+// symbol j the sum over the batch's realisations of c |e|^2 / pn_eff, e = x_est -
+// symbols[sidx[j][rep]] (real_detect: the real parts, c = 2; else c = 1), added
+// into acc_est[snr][stage][j] / acc_perf[snr][j].  k.scale is not read: the ratio
+// is against the AWGN pn_eff.  One block = one SNR point of the chunk x one stage
+// x one tile of LLR_CALIB_LT symbols; wave w takes the tile's symbols w, w + 4, ..
+// and walks the SNR point's unit waves in order, lane = unit, one fp64 sum per
+// symbol and lane, then one butterfly per symbol.  Every accumulator entry has
+// one writer per launch and a fixed order of terms: no atomics, and the sums of
+// two identical calls are bit-identical.
+constexpr int LLR_CALIB_LT = 8;
+struct LlrCalibK {
+    LlrK k;
+    const double2* h;         // [LK][R] perfect-CSI diag(D) of the batch
+    const uint16_t* sidx;     // [ND][R] transmitted symbol indices
+    int st_lo, nst;
+    double* acc_est;          // [nsnr][S][ND], or null
+    double* acc_perf;         // [nsnr][ND], or null
+};
+void launch_llr_calib(hipStream_t s, const LlrCalibK& a);
 // LLRs of n points x (pn: one value or one per point), out [n][m]
 void launch_llr_probe(hipStream_t s, const LlrTab& t, const double2* x, const double* pn, long long n_pn, long long n,
                       bool maxlog, double* out);

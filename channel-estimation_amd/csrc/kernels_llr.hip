@@ -3,7 +3,9 @@
 // (k_llr_probe; dsce_llr_awgn) and in bulk for every stage of the MMSE branch
 // (k_llr; dsce_export_llr), and the BICM information loss summed from those LLRs
 // on the device (k_llr_info + k_llr_info_sum; dsce_run_soft).  One device
-// function, llr_demap, serves all of them.
+// function, llr_demap, serves all of them.  k_llr_calib (dsce_run_calib) sums the
+// demapper error against the transmitted symbol over pn_eff instead; it shares
+// the demapper input (llr_input) with the two bulk kernels.
 //
 //   LLR_b(x, pn) = log sum_{bit_b = 1} exp(-e_i) - log sum_{bit_b = 0} exp(-e_i),   e_i = |x - s_i|^2 / pn
 //
@@ -168,6 +170,37 @@ void launch_llr_probe(hipStream_t s, const LlrTab& t, const double2* x, const do
     hipLaunchKernelGGL(k_llr_probe, dim3(blocks), dim3(256), 0, s, t, x, pn, n_pn, n, maxlog ? 1 : 0, out);
 }
 
+// The demapper input of data symbol j for the lane's unit, as include/dsce.h
+// defines it: x_est and the AWGN pn_eff from row(s) base + l of y [..][U] at
+// `unit` and of h [..][hU] at `hunit` (h_est of the stage, or the batch's
+// perfect-CSI diag(D) for the pseudo-stage).  One statement sequence for k_llr,
+// k_llr_info and k_llr_calib, so the three form the same bits.
+__device__ __forceinline__ void llr_input(const LlrK& a, const double2* __restrict__ hsrc, size_t base, size_t U,
+                                          size_t unit, size_t hU, size_t hunit, int j, double pnk, double2& x,
+                                          double& pe) {
+    if (a.despread) {                                      // x = P^H (y ./ h), row NP + j of P^H
+        double2 acc = make_double2(0.0, 0.0);
+        double pacc = 0.0;
+        const int j0 = a.ph_ptr[a.NP + j], j1 = a.ph_ptr[a.NP + j + 1];
+        for (int jj = j0; jj < j1; ++jj) {
+            const int l = a.ph_col[jj];
+            const double2 pv = a.ph_val[jj];
+            const double2 y = a.yic[(base + l) * U + unit], h = hsrc[(base + l) * hU + hunit];
+            c_fma(acc, pv, c_div(y, h));
+            pacc += (pv.x * pv.x + pv.y * pv.y) * (pnk * a.qn[l]) / (h.x * h.x + h.y * h.y);
+        }
+        x = make_double2(acc.x / a.data_div, acc.y / a.data_div);
+        pe = pacc / (a.data_div * a.data_div);
+    } else {
+        const int l = a.data_pos[j];
+        const double2 y = a.yic[(base + l) * U + unit], h = hsrc[(base + l) * hU + hunit];
+        const double2 q = c_div(y, h);
+        x = make_double2(q.x / a.data_div, q.y / a.data_div);
+        pe = pnk * a.qn[l] / ((h.x * h.x + h.y * h.y) * (a.data_div * a.data_div));
+    }
+    if (a.real_detect) x.y = 0.0;
+}
+
 // k_llr — the sibling of k_export_stages for the soft outputs.  One block = 64
 // consecutive units (one SNR point) x one tile of LT data symbols of one stage.
 // Phase 1, lane = unit, wave w the tile's symbols w, w + 4, ..: y_ic and h_est of
@@ -203,27 +236,8 @@ __global__ void __launch_bounds__(256) k_llr(LlrK a) {
         if (j >= a.ND) break;                              // wave-uniform
         double2 x;
         double pe;
-        if (a.despread) {                                  // x = P^H (y ./ h), row NP + j of P^H
-            double2 acc = make_double2(0.0, 0.0);
-            double pacc = 0.0;
-            const int j0 = a.ph_ptr[a.NP + j], j1 = a.ph_ptr[a.NP + j + 1];
-            for (int jj = j0; jj < j1; ++jj) {
-                const int l = a.ph_col[jj];
-                const double2 pv = a.ph_val[jj];
-                const double2 y = a.yic[(base + l) * U + unit], h = a.hest[(base + l) * U + unit];
-                c_fma(acc, pv, c_div(y, h));
-                pacc += (pv.x * pv.x + pv.y * pv.y) * (pnk * a.qn[l]) / (h.x * h.x + h.y * h.y);
-            }
-            x = make_double2(acc.x / a.data_div, acc.y / a.data_div);
-            pe = pacc / (a.data_div * a.data_div);
-        } else {
-            const int l = a.data_pos[j];
-            const double2 y = a.yic[(base + l) * U + unit], h = a.hest[(base + l) * U + unit];
-            const double2 q = c_div(y, h);
-            x = make_double2(q.x / a.data_div, q.y / a.data_div);
-            pe = pnk * a.qn[l] / ((h.x * h.x + h.y * h.y) * (a.data_div * a.data_div));
-        }
-        if (a.real_detect) x.y = 0.0;
+        llr_input(a, a.hest, base, U, unit, U, unit, j, pnk, x, pe);
+        if (a.scale) pe = a.scale[((size_t)snr * a.S + stage) * a.ND + j] * pe;   // wave-uniform load
         xt[lane * XS + e] = x;
         pt[lane * XS + e] = pe;
         if (want_llr) {
@@ -288,8 +302,8 @@ __device__ __forceinline__ double info_loss_nats(double llr, bool bit) {
     return fmax(-z, 0.0) + log1p(exp(-fabs(z)));
 }
 
-// k_llr_info — k_llr with a sum in place of the stores.  Phase 1 is k_llr's,
-// statement for statement (lane = unit, wave w the tile's symbols w, w + 4, ..),
+// k_llr_info — k_llr with a sum in place of the stores.  Phase 1 is k_llr's
+// (llr_input; lane = unit, wave w the tile's symbols w, w + 4, ..),
 // with the channel of pseudo-stage S read from h[l][rep]; the store callback
 // adds the bit's loss, in nats, to the lane's two fp64 sums (all symbols,
 // considered symbols) with the transmitted index sidx[j][rep], contiguous across
@@ -316,6 +330,9 @@ __global__ void __launch_bounds__(256) k_llr_info(LlrInfoK q) {
     const double2* hsrc = perf ? q.h : a.hest;
     const size_t hU = perf ? (size_t)a.R : U, hunit = perf ? (size_t)rep : unit;
     const double pnk = a.pn[snr];
+    // the scale row of (snr, stage): dsce_set_llr_scale's g_est, g_perf0 for the pseudo-stage
+    const double* scale = perf ? (q.scale_perf ? q.scale_perf + (size_t)snr * a.ND : nullptr)
+                               : (a.scale ? a.scale + ((size_t)snr * a.S + stage) * a.ND : nullptr);
     double sum_all = 0.0, sum_con = 0.0;
     if (rl0 < a.rvalid)                                    // else a wave of tail padding (block-uniform)
         for (int e = w; e < LT; e += 4) {
@@ -323,27 +340,8 @@ __global__ void __launch_bounds__(256) k_llr_info(LlrInfoK q) {
             if (j >= a.ND) break;                          // wave-uniform
             double2 x;
             double pe;
-            if (a.despread) {                              // x = P^H (y ./ h), row NP + j of P^H
-                double2 acc = make_double2(0.0, 0.0);
-                double pacc = 0.0;
-                const int j0 = a.ph_ptr[a.NP + j], j1 = a.ph_ptr[a.NP + j + 1];
-                for (int jj = j0; jj < j1; ++jj) {
-                    const int l = a.ph_col[jj];
-                    const double2 pv = a.ph_val[jj];
-                    const double2 y = a.yic[(base + l) * U + unit], h = hsrc[(base + l) * hU + hunit];
-                    c_fma(acc, pv, c_div(y, h));
-                    pacc += (pv.x * pv.x + pv.y * pv.y) * (pnk * a.qn[l]) / (h.x * h.x + h.y * h.y);
-                }
-                x = make_double2(acc.x / a.data_div, acc.y / a.data_div);
-                pe = pacc / (a.data_div * a.data_div);
-            } else {
-                const int l = a.data_pos[j];
-                const double2 y = a.yic[(base + l) * U + unit], h = hsrc[(base + l) * hU + hunit];
-                const double2 qt = c_div(y, h);
-                x = make_double2(qt.x / a.data_div, qt.y / a.data_div);
-                pe = pnk * a.qn[l] / ((h.x * h.x + h.y * h.y) * (a.data_div * a.data_div));
-            }
-            if (a.real_detect) x.y = 0.0;
+            llr_input(a, hsrc, base, U, unit, hU, hunit, j, pnk, x, pe);
+            if (scale) pe = scale[j] * pe;                 // wave-uniform load
             const unsigned t = q.sidx[(size_t)j * a.R + rep];
             double sym = 0.0;
             llr_demap(a.tab, x, pe, a.maxlog != 0, [&](int b, double v) { sym += info_loss_nats(v, (t >> b) & 1); });
@@ -389,6 +387,72 @@ void launch_llr_info(hipStream_t s, const LlrInfoK& a) {
     hipLaunchKernelGGL(k_llr_info, dim3(a.k.U / 64, a.nst * ntile), dim3(256), 0, s, a);
     const int n = (a.k.U / a.k.R) * a.nst * 2;
     hipLaunchKernelGGL(k_llr_info_sum, dim3((n + 63) / 64), dim3(64), 0, s, a, (a.k.R / 64) * ntile, n);
+}
+
+// k_llr_calib — the demapper noise ratio per data symbol, summed over the
+// realisations.  Phase 1 is k_llr_info's (llr_input; lane = unit, element-major
+// reads, pseudo-stage S from h[l][rep]); in place of llr_demap one lookup of the
+// transmitted symbol and c |e|^2 / pn_eff.  The sum runs over the lanes and
+// stays per symbol, so a block owns (SNR point, stage, tile of LLR_CALIB_LT
+// symbols) and its waves walk the SNR point's R / 64 unit waves themselves: the
+// per-lane sums live in registers (LLR_CALIB_LT / 4 per lane, statically
+// indexed), one butterfly per symbol at the end, and lane 0 adds the result to
+// the call's device accumulator, which no other block of the launch touches.
+__global__ void __launch_bounds__(256) k_llr_calib(LlrCalibK q) {
+    constexpr int LT = LLR_CALIB_LT, PER = LT / 4;
+    const LlrK& a = q.k;
+    const int ntile = (a.ND + LT - 1) / LT;
+    const int st = blockIdx.y / ntile, e0 = (blockIdx.y % ntile) * LT;
+    const int stage = q.st_lo + st;
+    const bool perf = stage == a.S;                        // the perfect-CSI one-tap receiver
+    const int sc = blockIdx.x, snr = a.snr0 + sc;          // SNR point of the chunk
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const size_t U = (size_t)a.U;
+    const size_t base = perf ? 0 : (size_t)stage * a.LK;   // perfect CSI: y = stage 0 of y_ic
+    const double2* hsrc = perf ? q.h : a.hest;
+    const size_t hU = perf ? (size_t)a.R : U;
+    const double pnk = a.pn[snr];
+    const double c = a.real_detect ? 2.0 : 1.0;            // a real observation has variance pn_eff / 2
+    double sum[PER];
+#pragma unroll
+    for (int i = 0; i < PER; ++i) sum[i] = 0.0;
+    for (int rl0 = 0; rl0 < a.rvalid; rl0 += 64) {         // the SNR point's unit waves, in order
+        const int rep = rl0 + lane;
+        const bool counts = rep < a.rvalid;                // a padding realisation adds nothing
+        const size_t unit = (size_t)sc * a.R + rep;
+        const size_t hunit = perf ? (size_t)rep : unit;
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            const int j = e0 + w + 4 * i;
+            if (j >= a.ND) break;                          // wave-uniform
+            double2 x;
+            double pe;
+            llr_input(a, hsrc, base, U, unit, hU, hunit, j, pnk, x, pe);
+            const unsigned t = counts ? q.sidx[(size_t)j * a.R + rep] : 0u;
+            const double2 s = a.tab.symbols[t];
+            const double dx = x.x - s.x, dy = a.real_detect ? 0.0 : x.y - s.y;
+            const double r = c * (dx * dx + dy * dy) / pe;
+            if (counts) sum[i] += r;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        double v = sum[i];
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+        const int j = e0 + w + 4 * i;
+        if (lane == 0 && j < a.ND) {
+            double* dst = perf ? q.acc_perf + (size_t)snr * a.ND + j : q.acc_est + ((size_t)snr * a.S + stage) * a.ND + j;
+            *dst += v;
+        }
+    }
+}
+
+void launch_llr_calib(hipStream_t s, const LlrCalibK& a) {
+    if (a.nst <= 0) return;
+    const int ntile = (a.k.ND + LLR_CALIB_LT - 1) / LLR_CALIB_LT;
+    hipLaunchKernelGGL(k_llr_calib, dim3(a.k.U / a.k.R, a.nst * ntile), dim3(256), 0, s, a);
 }
 
 }  // namespace dsce

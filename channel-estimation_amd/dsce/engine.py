@@ -28,6 +28,7 @@ EXPORTED = [
     "dsce_kernel_work", "dsce_structured_check", "dsce_create_multi", "dsce_group_info",
     "dsce_transmission_matrix", "dsce_jakes_info", "dsce_export", "dsce_export_stages",
     "dsce_llr_awgn", "dsce_export_llr", "dsce_llr_info", "dsce_run_soft",
+    "dsce_run_calib", "dsce_set_llr_scale", "dsce_get_llr_scale",
 ]
 
 ABI_VERSION = 10
@@ -108,6 +109,10 @@ class SoftOut(C.Structure):
     _fields_ = [("loss_est", C.POINTER(C.c_double)), ("loss_perf0", C.POINTER(C.c_double))]
 
 
+class CalibOut(C.Structure):
+    _fields_ = [("ratio_est", C.POINTER(C.c_double)), ("ratio_perf0", C.POINTER(C.c_double))]
+
+
 class TxDesc(C.Structure):
     _fields_ = [("kind", C.c_int32), ("n_subcarriers", C.c_int32), ("n_symbols", C.c_int32),
                 ("n_samples", C.c_int32), ("fft_size", C.c_int32), ("intermediate_bin", C.c_int32),
@@ -179,6 +184,9 @@ def load_library(path=None):
                                     C.POINTER(ExportLlrOut)]
     lib.dsce_llr_info.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32)]
     lib.dsce_run_soft.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(SoftOut)]
+    lib.dsce_run_calib.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(CalibOut)]
+    lib.dsce_set_llr_scale.argtypes = [vp, C.c_int32, dp, dp]
+    lib.dsce_get_llr_scale.argtypes = [vp, C.c_int32, dp, dp, C.POINTER(C.c_int32)]
     for name in EXPORTED:
         fn = getattr(lib, name)
         if name != "dsce_last_error":
@@ -584,6 +592,65 @@ class Engine:
         m = self.llr_info(sid)["m"]
         nd = self.bits_per_rep(sid).astype(np.float64) / m
         return m - np.asarray(loss, dtype=np.float64) / (float(n_rep) * nd)
+
+    # -- measured demapper noise (DSCE_HAS_LLR_SCALE) ---------------------------------
+    def calib_shapes(self, sid):
+        """Shapes of dsce_run_calib's arrays, and of the scale tables, for scheme sid."""
+        d = self.scheme_dims(sid)
+        return dict(ratio_est=(d.n_snr, d.n_iter + 1, d.n_data), ratio_perf0=(d.n_snr, d.n_data))
+
+    def run_calib(self, sid, seed, first_rep, n_rep, out=None):
+        """Demapper noise ratio of realisations [first_rep, first_rep + n_rep) of
+        scheme sid, summed on the GPU (dsce_run_calib): dict of float64 arrays
+        ratio_est [n_snr][S][ND] (MMSE branch, per stage and data symbol) and
+        ratio_perf0 [n_snr][ND] (perfect-CSI one-tap receiver): the sums over the
+        realisations of c |x_est - s_tx|^2 / pn_eff with the unscaled AWGN pn_eff
+        (dsce.modulation.demapper_noise_ratio); rho = ratio / n_rep is what
+        set_llr_scale takes.  The sums are ADDED into the arrays of `out` (a dict
+        with either or both keys, C-contiguous float64; only the given ones are
+        computed) and `out` is returned; without it both are computed from zero."""
+        shapes = self.calib_shapes(sid)
+        if out is None:
+            out = {f: np.zeros(shp) for f, shp in shapes.items()}
+        o = CalibOut()
+        for f, a in out.items():
+            if f not in shapes:
+                raise ValueError("unknown calibration output %r (of %s)" % (f, list(shapes)))
+            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous
+                    and a.shape == shapes[f]):
+                raise ValueError("%s must be a C-contiguous float64 array of shape %s" % (f, shapes[f]))
+            setattr(o, f, _dptr(a))
+        self._chk(self.lib.dsce_run_calib(self.h, int(sid), int(seed), int(first_rep), int(n_rep), 0, C.byref(o)),
+                  "dsce_run_calib")
+        return out
+
+    def set_llr_scale(self, sid, g_est=None, g_perf0=None):
+        """Install the scale tables of scheme sid (dsce_set_llr_scale): g_est
+        [n_snr][S][ND] multiplies pn_eff in export_llr and in run_soft's loss_est,
+        g_perf0 [n_snr][ND] in run_soft's loss_perf0; None removes a table.  Every
+        entry finite and > 0.  set_snr drops the tables."""
+        shapes = self.calib_shapes(sid)
+        ptr = []
+        for g, f in ((g_est, "ratio_est"), (g_perf0, "ratio_perf0")):
+            if g is None:
+                ptr.append(None)
+                continue
+            g = np.ascontiguousarray(g, dtype=np.float64)
+            if g.shape != shapes[f]:
+                raise ValueError("scale table must have shape %s" % (shapes[f],))
+            ptr.append(g)
+        self._chk(self.lib.dsce_set_llr_scale(self.h, int(sid), *(None if g is None else _dptr(g) for g in ptr)),
+                  "dsce_set_llr_scale")
+
+    def llr_scale(self, sid):
+        """dict(g_est, g_perf0, set) of scheme sid (dsce_get_llr_scale): the installed
+        tables (ones where none is installed) and set = (bool, bool)."""
+        shapes = self.calib_shapes(sid)
+        g_est, g_perf0 = np.zeros(shapes["ratio_est"]), np.zeros(shapes["ratio_perf0"])
+        set2 = (C.c_int32 * 2)()
+        self._chk(self.lib.dsce_get_llr_scale(self.h, int(sid), _dptr(g_est), _dptr(g_perf0), set2),
+                  "dsce_get_llr_scale")
+        return dict(g_est=g_est, g_perf0=g_perf0, set=(bool(set2[0]), bool(set2[1])))
 
     # -- engine state ------------------------------------------------------------
     def scheme_dims(self, sid):

@@ -439,3 +439,22 @@ def bicm_info_loss(llr, bits):
     llr = np.asarray(llr, dtype=float)
     z = np.where(np.asarray(bits).astype(bool), llr, -llr)
     return (np.maximum(-z, 0.0) + np.log1p(np.exp(-np.abs(z)))) / np.log(2.0)
+
+
+def demapper_noise_ratio(x_est, pn_eff, sym, symbols, real_detect=False):
+    """Per-term demapper noise ratio c |e|^2 / pn_eff of the demapper inputs x_est
+    (complex, any leading shape) with the AWGN noise powers pn_eff against the
+    transmitted symbols symbols[sym] (x_est, pn_eff and sym broadcast against each
+    other): e = x_est - s_tx with c = 1, or with real_detect e = Re(x_est) -
+    Re(s_tx) with c = 2 (a real observation has variance pn_eff / 2).  Its mean
+    over realisations is rho: 1 where the AWGN model of LLR_AWGN holds, 1 + the
+    residual interference and estimation error to noise ratio otherwise.  The
+    definition that dsce_run_calib (include/dsce.h) sums on the GPU."""
+    s = np.asarray(symbols, dtype=complex).reshape(-1)[np.asarray(sym)]
+    x = np.asarray(x_est, dtype=complex)
+    pn = np.asarray(pn_eff, dtype=float)
+    if real_detect:
+        d = x.real - s.real
+        return 2.0 * (d * d) / pn
+    d = x - s
+    return (d.real * d.real + d.imag * d.imag) / pn

@@ -64,9 +64,16 @@ def main(argv=None):
     ap.add_argument("--rate", choices=("exact", "maxlog"), default=None,
                     help="also the BICM rate per scheme, SNR point and IC stage from the demapper's LLRs "
                          "(exact, or max-log: the mismatched-decoder rate), summed on the GPU (dsce_run_soft)")
+    ap.add_argument("--calibrate", action="store_true",
+                    help="with --rate: measure the demapper noise ratio rho per SNR point, stage and data symbol "
+                         "over the same realisations (dsce_run_calib), scale pn_eff by it (dsce_set_llr_scale) and "
+                         "report the rate of the scaled LLRs too.  rho is in-sample: the calibrated rate is biased "
+                         "upward by O(1 / reps), so a sweep wants thousands of realisations")
     a = ap.parse_args(argv)
     if (a.resume or a.stop_after is not None) and not a.checkpoint:
         raise SystemExit("--resume / --stop-after need --checkpoint")
+    if a.calibrate and not a.rate:
+        raise SystemExit("--calibrate needs --rate")
     if a.rate:
         # the rate pass is one plain sweep of the rank's realisations after the counters
         for on, what in ((a.checkpoint, "--checkpoint (the rate sums are not checkpointed)"),
@@ -126,6 +133,12 @@ def main(argv=None):
     loss_e = np.zeros((len(names), nsnr, nst, 2))
     loss_p = np.zeros((len(names), nsnr, 2))
     bits, rate_s = None, 0.0
+    # --calibrate: the ratio sums and the losses of the scaled LLRs
+    n_data = [int(S.schemes[s].n_data) for s in names]
+    ratio_e = [np.zeros((nsnr, nst, nd)) for nd in n_data]
+    ratio_p = [np.zeros((nsnr, nd)) for nd in n_data]
+    closs_e, closs_p = np.zeros_like(loss_e), np.zeros_like(loss_p)
+    eng = None
     setup_s, t0 = 0.0, time.perf_counter()
     ck_path = None
     if a.checkpoint:
@@ -180,7 +193,27 @@ def main(argv=None):
                 out = {"loss_est": loss_e[i], "loss_perf0": loss_p[i]}
                 for at in range(0, mine, step):
                     eng.run_soft(i, a.seed, first + at, min(step, mine - at), a.rate, out)
+            if a.calibrate:
+                for i in range(len(names)):
+                    out = {"ratio_est": ratio_e[i], "ratio_perf0": ratio_p[i]}
+                    for at in range(0, mine, step):
+                        eng.run_calib(i, a.seed, first + at, min(step, mine - at), out)
             rate_s = time.perf_counter() - t1
+    if a.calibrate:
+        # rho = ratio / reps over every rank's realisations (the sums are exchanged like the MSE sums; --rate
+        # excludes checkpoints, so every rank gets here), installed on every rank, then the rate pass again
+        t1 = time.perf_counter()
+        if distributed:
+            dev = "cuda" if os.environ.get("DSCE_DIST_BACKEND", "nccl") == "nccl" else None
+            ratio_e = [allreduce_counts(r, dev) for r in ratio_e]
+            ratio_p = [allreduce_counts(r, dev) for r in ratio_p]
+        for i in range(len(names) if mine else 0):
+            eng.set_llr_scale(i, ratio_e[i] / reps, ratio_p[i] / reps)
+            out = {"loss_est": closs_e[i], "loss_perf0": closs_p[i]}
+            for at in range(0, mine, step):
+                eng.run_soft(i, a.seed, first + at, min(step, mine - at), a.rate, out)
+        rate_s += time.perf_counter() - t1
+    if eng is not None:
         eng.close()
     complete = done >= mine
     if distributed:
@@ -220,6 +253,9 @@ def main(argv=None):
         if a.rate:
             loss_e = allreduce_counts(loss_e, dev)
             loss_p = allreduce_counts(loss_p, dev)
+        if a.calibrate:
+            closs_e = allreduce_counts(closs_e, dev)
+            closs_p = allreduce_counts(closs_p, dev)
         # bits per realisation are a property of the schemes: every rank with work
         # has them (collective on every rank, so a rank with an empty shard too)
         have = np.array([0 if bits is None else 1], dtype=np.int64)
@@ -247,6 +283,20 @@ def main(argv=None):
                 "mmse": {e: (m - loss_e[i, :, :, k] / (reps * nd[k])).tolist() for k, e in enumerate(EDGE)},
                 "perfect_onetap": {e: (m - loss_p[i, :, k] / (reps * nd[k])).tolist() for k, e in enumerate(EDGE)},
                 "method": a.rate}
+            if a.calibrate:
+                # the same with pn_eff <- rho pn_eff; noise_ratio: the mean rho over the symbols of each edge class
+                cons = np.asarray(S.schemes[s].considered_symbols).astype(bool)
+                sel = (np.ones_like(cons), cons)
+                extra["bicm_rate"][s].update({
+                    "mmse_calibrated": {e: (m - closs_e[i, :, :, k] / (reps * nd[k])).tolist()
+                                        for k, e in enumerate(EDGE)},
+                    "perfect_onetap_calibrated": {e: (m - closs_p[i, :, k] / (reps * nd[k])).tolist()
+                                                  for k, e in enumerate(EDGE)},
+                    "noise_ratio": {"mmse": {e: (ratio_e[i][:, :, sel[k]].mean(axis=-1) / reps).tolist()
+                                             for k, e in enumerate(EDGE)},
+                                    "perfect_onetap": {e: (ratio_p[i][:, sel[k]].mean(axis=-1) / reps).tolist()
+                                                       for k, e in enumerate(EDGE)}},
+                    "calibration": {"reps": int(reps), "in_sample": True}})
     extra["realisations_per_s"] = reps / extra["seconds"]
     res = results.make(S, names, counts, bits, reps, a.seed, extra=extra)
     if rank != 0:
@@ -268,7 +318,9 @@ def main(argv=None):
         print(json.dumps({s: {"snr_db": float(S.snr_db[k]), "method": a.rate,
                               "bicm_rate_ic_mmse": r["mmse"]["all"][k][-1],
                               "bicm_rate_onetap_mmse": r["mmse"]["all"][k][0],
-                              "bicm_rate_onetap_perfect": r["perfect_onetap"]["all"][k]}
+                              "bicm_rate_onetap_perfect": r["perfect_onetap"]["all"][k],
+                              **({"bicm_rate_ic_mmse_calibrated": r["mmse_calibrated"]["all"][k][-1]}
+                                 if a.calibrate else {})}
                           for s, r in extra["bicm_rate"].items()}))
     if distributed:
         dist.destroy_process_group()

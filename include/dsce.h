@@ -41,6 +41,8 @@
  *                            of the MMSE branch                  script:429-444, :519-525
  *   dsce_run_soft         <- no counterpart in the script: the BICM rate of those LLRs
  *                            against the BITS stream, summed per SNR point and stage
+ *   dsce_run_calib        <- no counterpart in the script: the demapper error against the
+ *                            transmitted symbols over pn_eff, per position
  *
  * Conventions
  *  - Return 0 on success, a negative DSCE_E* code on failure; the message is
@@ -90,6 +92,9 @@
  * dsce_export_llr and dsce_llr_info: soft outputs of the demapper.
  * DSCE_HAS_SOFT_RUN (still ABI 10) announces dsce_run_soft: the BICM information
  * loss of those LLRs, summed on the device.
+ * DSCE_HAS_LLR_SCALE (still ABI 10) announces dsce_run_calib, dsce_set_llr_scale
+ * and dsce_get_llr_scale: the demapper noise measured against the transmitted
+ * symbols, and the soft calls' pn_eff scaled by it.
  */
 #ifndef DSCE_H
 #define DSCE_H
@@ -567,6 +572,66 @@ typedef struct {          /* each optional */
  * On a multi-device handle the call is member 0's. */
 int dsce_run_soft(dsce_ctx* ctx, int32_t scheme_id, uint64_t seed, uint64_t first_rep, uint64_t n_rep,
                   uint32_t flags, const dsce_soft_out* out);
+
+/* ---- measured demapper noise (DSCE_HAS_LLR_SCALE; additive, ABI 10) ------- */
+/* Definitions, for scheme sid, SNR point k, stage s and data symbol j, with
+ * S = 1 + n_iter; x_est, pn_eff and the symbol table are those of the soft-output
+ * section above, and s_t = symbols[sym[rep][j]] is the transmitted symbol (the
+ * sym of dsce_export):
+ *    e = x_est - s_t,          c = 1   (complex detection)
+ *    e = Re(x_est) - Re(s_t),  c = 2   (real_detect: a real observation has
+ *                                       variance pn_eff / 2)
+ *    ratio_est[k][s][j] = sum over the call's realisations of c |e|^2 / pn_eff,
+ *                         MMSE branch, with the unscaled AWGN pn_eff;
+ *    ratio_perf0[k][j]  = the same for the perfect-CSI one-tap receiver (y and h
+ *                         of dsce_export, as loss_perf0);
+ *    rho = ratio / n_rep.
+ *  rho = 1 would mean that the AWGN model of LLR_AWGN holds; rho - 1 is the
+ *  residual interference plus estimation error to noise ratio of the position.
+ *  The sum is normalised per realisation by pn_eff and not averaged in the x
+ *  domain: E[1 / |h|^2] diverges under Rayleigh fading, while the AWGN and the
+ *  interference in x_est both scale as 1 / |h_est|^2, so the ratio is what stays
+ *  stable.
+ *  What rho is not: it is a second-moment match.  The interference is neither
+ *  Gaussian nor independent of h, so with exact LLRs and pn_eff <- rho pn_eff the
+ *  figure of dsce_run_soft is still the rate of a mismatched decoder, only no
+ *  longer an absurd one (at high SNR the unscaled figure is far below zero). */
+#define DSCE_HAS_LLR_SCALE 1
+typedef struct {            /* each optional */
+    double* ratio_est;      /* [n_snr][1 + n_iter][ND] */
+    double* ratio_perf0;    /* [n_snr][ND]             */
+} dsce_calib_out;
+
+/* ADDS the sums defined above into the caller's host arrays, as dsce_run_soft
+ * does.  The run is dsce_run_soft's (the same realisations for the same seed;
+ * batches, SNR chunks, the export_stage_mb cut, padding realisations that
+ * contribute nothing, any n_rep >= 0 with n_rep = 0 adding nothing, no change to
+ * the error counters, the MSE sums or dsce_path_info), with "k_llr_calib" (its
+ * name under dsce_enable_timing) after each SNR chunk: summed on the device in
+ * a fixed order without atomics, so two identical calls return identical bits.
+ * It always measures against the unscaled pn_eff: a call with tables installed
+ * returns the bits of a call without.  flags must be 0: any bit is DSCE_EINVAL,
+ * as are a null out and no field requested.  DSCE_ESTATE as for dsce_run_soft.
+ * On a multi-device handle the call is member 0's. */
+int dsce_run_calib(dsce_ctx* ctx, int32_t scheme_id, uint64_t seed, uint64_t first_rep, uint64_t n_rep,
+                   uint32_t flags, const dsce_calib_out* out);
+
+/* Installs device-resident scale tables g_est [n_snr][1 + n_iter][ND] and
+ * g_perf0 [n_snr][ND] (C order; typically rho) for a scheme; a null argument
+ * removes that table.  While g_est is installed dsce_export_llr forms
+ * pn_eff <- g_est[k][s][j] pn_eff: the exported pn_eff is the scaled one, the
+ * LLRs use it, x_est is unchanged to the bit; dsce_run_soft does the same for
+ * loss_est and uses g_perf0 for loss_perf0.  dsce_llr_awgn takes the caller's
+ * pn and is untouched.  Every entry must be finite and > 0, else DSCE_EINVAL and
+ * the installed tables stay as they were.  Needs dsce_set_snr (DSCE_ESTATE) and
+ * the scheme, not dsce_build_mmse; dsce_set_snr drops the tables of every
+ * scheme, because their shape is its arguments.  A configuration call: on a
+ * multi-device handle it reaches every member. */
+int dsce_set_llr_scale(dsce_ctx* ctx, int32_t scheme_id, const double* g_est, const double* g_perf0);
+/* set2[0] / set2[1] = 1 where g_est / g_perf0 is installed; the tables are
+ * copied out, 1.0 everywhere for one that is not installed.  Every pointer
+ * optional.  DSCE_ESTATE before dsce_set_snr. */
+int dsce_get_llr_scale(dsce_ctx* ctx, int32_t scheme_id, double* g_est, double* g_perf0, int32_t* set2);
 
 /* ---- engine state ------------------------------------------------------- */
 int dsce_scheme_dims(dsce_ctx* ctx, int32_t scheme_id, dsce_dims* dims);
