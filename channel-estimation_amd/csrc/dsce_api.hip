@@ -161,6 +161,9 @@ struct Scheme {
     double* g_est = nullptr;
     double* g_perf0 = nullptr;
     std::vector<double> g_est_host, g_perf0_host;
+    // dsce_set_llr_scale_perf: the same for the DSCE_LLR_PERFECT calls, [nsnr][1 + niter][ND]
+    double* g_perf = nullptr;
+    std::vector<double> g_perf_host;
 };
 
 }  // namespace dsce
@@ -1660,7 +1663,7 @@ void run_batch(dsce_ctx* c, uint64_t seed, uint64_t rep0, int R, int nvalid, Tra
     b.R = R;
     b.rvalid = nvalid;
     b.tr = nullptr;
-    b.tr_bulk = 0;
+    b.tr_bulk = b.tr_yperf = 0;
     unsigned long long* const counters = bk ? bk->counters : c->d_counters;
     {
         Timed t(c, "k_jakes");
@@ -1724,11 +1727,14 @@ void run_batch(dsce_ctx* c, uint64_t seed, uint64_t rep0, int R, int nvalid, Tra
                 DSCE_HIP_CHECK(hipMemcpyAsync(bk->dev, &bk->k, sizeof(TraceK), hipMemcpyHostToDevice, c->stream));
                 DSCE_HIP_CHECK(hipMemsetAsync(bk->k.yest, 0xff, ns * LK * U * sizeof(double2), c->stream));
                 DSCE_HIP_CHECK(hipMemsetAsync(bk->k.hest, 0xff, ns * LK * U * sizeof(double2), c->stream));
+                if (bk->k.yperf)
+                    DSCE_HIP_CHECK(hipMemsetAsync(bk->k.yperf, 0xff, ns * LK * U * sizeof(double2), c->stream));
                 DSCE_HIP_CHECK(hipMemsetAsync(bk->hp, 0xff, ns * NP * U * sizeof(double2), c->stream));
                 DSCE_HIP_CHECK(hipMemsetAsync(bk->k.dec_e, 0xff, ns * nd * U * sizeof(int), c->stream));
                 DSCE_HIP_CHECK(hipMemsetAsync(bk->k.dec_p, 0xff, ns * nd * U * sizeof(int), c->stream));
                 b.tr = bk->dev;
                 b.tr_bulk = 1;
+                b.tr_yperf = bk->k.yperf ? 1 : 0;
             }
             // device copy of a per-unit buffer into stage st of a bulk array (the host's copy_col of a trace)
             auto bulk_copy = [&](double2* dst, const double2* src, int st, int rows) {
@@ -1775,7 +1781,7 @@ void run_batch(dsce_ctx* c, uint64_t seed, uint64_t rep0, int R, int nvalid, Tra
                     bk->flush(s0);
                 }
                 b.tr = nullptr;
-                b.tr_bulk = 0;
+                b.tr_bulk = b.tr_yperf = 0;
                 continue;
             }
             // Otherwise one launch group per stage.  With the perfect-CSI branch
@@ -1833,6 +1839,7 @@ void run_batch(dsce_ctx* c, uint64_t seed, uint64_t rep0, int R, int nvalid, Tra
                         s.path |= launch_perfect_ic(c->stream, op, s.k, c->ch, b, pfuse ? &pd : nullptr);
                         if (to && to->yperf_stages && !pfuse)
                             copy_col(c, to->yperf_stages + (size_t)2 * it * LK, b.yperf, LK, b.U, tunit);
+                        if (bk && bk->k.yperf && !pfuse) bulk_copy(bk->k.yperf, b.yperf, it, LK);
                     }
                 }
                 {
@@ -1845,7 +1852,7 @@ void run_batch(dsce_ctx* c, uint64_t seed, uint64_t rep0, int R, int nvalid, Tra
             }
             if (bk) bk->flush(s0);
             b.tr = nullptr;
-            b.tr_bulk = 0;
+            b.tr_bulk = b.tr_yperf = 0;
         }
         if (bk) s.path = path_before;
     }
@@ -2019,10 +2026,11 @@ Scheme& bulk_export_check(dsce_ctx* ctx, int32_t id, const void* out, uint32_t f
 // export_stage_mb (every realisation is its own Philox streams: the cut does not
 // show).  launch(bk, snr0): the export kernel of the chunk that starts at SNR
 // index snr0, from the bulk arrays of bk into the sink's out[] at row0, for the
-// sub-batch in ctx->buf (R, rvalid, U).
+// sub-batch in ctx->buf (R, rvalid, U).  yperf (DSCE_LLR_PERFECT): y_perf of
+// every stage is staged too, [stage][LK][U], and counts towards the bound.
 template <class Launch>
 void bulk_export(dsce_ctx* ctx, Scheme& s, int32_t id, uint64_t seed, uint64_t first_rep, uint64_t n_rep,
-                 ExportSink& sink, Launch launch) {
+                 ExportSink& sink, Launch launch, bool yperf = false) {
     const std::string w(sink.what);
     sink.check(ctx, [&] {
         if (!(s.mmse_ready && s.Wd))
@@ -2034,7 +2042,8 @@ void bulk_export(dsce_ctx* ctx, Scheme& s, int32_t id, uint64_t seed, uint64_t f
     const int LK = s.LK, NP = s.d.n_pilots, ND = s.d.n_data, nsnr = ctx->nsnr, S = ctx->niter + 1;
     // the bulk trace arrays of one unit: hP, diag(D_hat), y_ic and both decisions of every stage
     const int chunk = snr_chunk(ctx);
-    const size_t unit_bytes = (size_t)S * (((size_t)NP + 2 * (size_t)LK) * sizeof(double2) + 2 * (size_t)ND * sizeof(int));
+    const size_t unit_bytes =
+        (size_t)S * (((size_t)NP + (yperf ? 3 : 2) * (size_t)LK) * sizeof(double2) + 2 * (size_t)ND * sizeof(int));
     const size_t bound = (size_t)ctx->op.export_stage_mb << 20;
     const size_t waves = std::max<size_t>(1, bound / (unit_bytes * 64 * (size_t)chunk));
     const int rsub = (int)std::min<size_t>((size_t)(ctx->batch + 63) / 64, waves) * 64;
@@ -2045,7 +2054,7 @@ void bulk_export(dsce_ctx* ctx, Scheme& s, int32_t id, uint64_t seed, uint64_t f
     bk.k.LK = LK;
     bk.k.ND = ND;
     bk.k.unit = 0;
-    bk.k.yperf = nullptr;
+    bk.k.yperf = yperf ? tmp.alloc<double2>(bk.units * S * LK) : nullptr;
     bk.k.yest = tmp.alloc<double2>(bk.units * S * LK);
     bk.k.hest = tmp.alloc<double2>(bk.units * S * LK);
     bk.k.dec_e = tmp.alloc<int>(bk.units * S * ND);
@@ -2445,6 +2454,11 @@ static void drop_llr_scale(dsce_ctx* ctx, Scheme& s) {
     s.g_est_host.clear();
     s.g_perf0_host.clear();
 }
+static void drop_llr_scale_perf(dsce_ctx* ctx, Scheme& s) {
+    if (s.g_perf) free_alloc(ctx, s.g_perf);
+    s.g_perf = nullptr;
+    s.g_perf_host.clear();
+}
 
 static int set_snr_one(dsce_ctx* ctx, const double* pn_time, int32_t n_snr, int32_t n_iter) {
     API_BEGIN
@@ -2460,6 +2474,7 @@ static int set_snr_one(dsce_ctx* ctx, const double* pn_time, int32_t n_snr, int3
         s->mmse_ready = false;
         if (s->interp) upload_interp(ctx, *s);
         drop_llr_scale(ctx, *s);                           // their shape was the previous arguments
+        drop_llr_scale_perf(ctx, *s);
     }
     const size_t n = ctx->schemes.size() * 4 * (size_t)n_snr * (n_iter + 1);
     ctx->counters_n = 0;
@@ -2838,12 +2853,17 @@ int dsce_export_stages(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_
 }
 
 // k_llr's arguments for the sub-batch in ctx->buf and the SNR chunk that starts
-// at snr0 (out, row0 and scale are the entry point's)
-static LlrK llr_args(dsce_ctx* ctx, const Scheme& s, const Bulk& bk, int snr0, bool maxlog) {
+// at snr0 (out and row0 are the entry point's).  perfect (DSCE_LLR_PERFECT): the
+// perfect-CSI branch, with its own scale table g_perf; else g_est.
+static LlrK llr_args(dsce_ctx* ctx, const Scheme& s, const Bulk& bk, int snr0, bool maxlog, bool perfect) {
     LlrK a{};
     a.tab = s.llr;
     a.yic = bk.k.yest;
     a.hest = bk.k.hest;
+    a.yperf = bk.k.yperf;
+    a.h = ctx->buf.h;
+    a.perfect = perfect ? 1 : 0;
+    a.scale = perfect ? s.g_perf : s.g_est;
     a.pn = ctx->d_pn;
     a.qn = s.qn;
     a.data_pos = s.k.data_pos;
@@ -2874,8 +2894,10 @@ int dsce_export_llr(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep
     TraceRange trace_range("dsce export llr");
     API_BEGIN
     check_ctx(ctx);
-    Scheme& s = bulk_export_check(ctx, id, out, flags, DSCE_EXPORT_F32 | DSCE_EXPORT_DEVICE | DSCE_LLR_MAXLOG,
+    Scheme& s = bulk_export_check(ctx, id, out, flags,
+                                  DSCE_EXPORT_F32 | DSCE_EXPORT_DEVICE | DSCE_LLR_MAXLOG | DSCE_LLR_PERFECT,
                                   "dsce_export_llr");
+    const bool perfect = (flags & DSCE_LLR_PERFECT) != 0;
     const bool f32 = (flags & DSCE_EXPORT_F32) != 0, to_device = (flags & DSCE_EXPORT_DEVICE) != 0;
     const int ND = s.d.n_data, nsnr = ctx->nsnr, S = ctx->niter + 1, m = s.d.bits_per_symbol;
     const size_t rsz = f32 ? sizeof(float) : sizeof(double);
@@ -2884,13 +2906,12 @@ int dsce_export_llr(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep
     ExportSink sink{"dsce_export_llr", 3, {out->x_est, out->pn_eff, out->llr}, {per, per, per * m}, {2 * rsz, rsz, rsz},
                     to_device};
     bulk_export(ctx, s, id, seed, first_rep, n_rep, sink, [&](const Bulk& bk, int snr0) {
-        LlrK a = llr_args(ctx, s, bk, snr0, (flags & DSCE_LLR_MAXLOG) != 0);
-        a.scale = s.g_est;
+        LlrK a = llr_args(ctx, s, bk, snr0, (flags & DSCE_LLR_MAXLOG) != 0, perfect);
         a.row0 = sink.row0;
         for (int i = 0; i < 3; ++i) a.out[i] = sink.out[i];
         Timed t(ctx, "k_llr");
         launch_llr(ctx->stream, a, f32);
-    });
+    }, perfect);
     API_END
 }
 
@@ -2909,7 +2930,10 @@ int dsce_run_soft(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, 
     TraceRange trace_range("dsce run soft");
     API_BEGIN
     check_ctx(ctx);
-    Scheme& s = bulk_export_check(ctx, id, out, flags, DSCE_LLR_MAXLOG, "dsce_run_soft");
+    Scheme& s = bulk_export_check(ctx, id, out, flags, DSCE_LLR_MAXLOG | DSCE_LLR_PERFECT, "dsce_run_soft");
+    const bool perfect = (flags & DSCE_LLR_PERFECT) != 0;
+    if (perfect && out->loss_perf0)
+        throw ApiError(DSCE_EINVAL, "dsce_run_soft: loss_perf0 with DSCE_LLR_PERFECT (it is stage 0 of loss_est)");
     const int ND = s.d.n_data, nsnr = ctx->nsnr, S = ctx->niter + 1;
     ExportSink sink{"dsce_run_soft", 2, {out->loss_est, out->loss_perf0}, {0, 0}, {sizeof(double), sizeof(double)}, false};
     const size_t n_est = out->loss_est ? (size_t)nsnr * S * 2 : 0, n_perf = out->loss_perf0 ? (size_t)nsnr * 2 : 0;
@@ -2929,17 +2953,15 @@ int dsce_run_soft(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, 
     }
     bulk_export(ctx, s, id, seed, first_rep, n_rep, sink, [&](const Bulk& bk, int snr0) {
         LlrK& a = q.k;
-        a = llr_args(ctx, s, bk, snr0, (flags & DSCE_LLR_MAXLOG) != 0);
-        a.scale = s.g_est;
+        a = llr_args(ctx, s, bk, snr0, (flags & DSCE_LLR_MAXLOG) != 0, perfect);
         q.scale_perf = s.g_perf0;
-        q.h = ctx->buf.h;
         q.sidx = ctx->buf.sidx;
         q.considered = s.k.considered;
         if (a.R > (ctx->batch + 63) / 64 * 64 || a.U / a.R > snr_chunk(ctx))
             throw ApiError(DSCE_EINVAL, "dsce_run_soft: partial sums too small");
         Timed t(ctx, "k_llr_info");
         launch_llr_info(ctx->stream, q);
-    });
+    }, perfect);
     if (n_rep > 0 && !host.empty()) {
         DSCE_HIP_CHECK(hipMemcpyAsync(host.data(), q.acc_est ? q.acc_est : q.acc_perf, host.size() * sizeof(double),
                                       hipMemcpyDeviceToHost, ctx->stream));
@@ -2962,7 +2984,10 @@ int dsce_run_calib(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep,
     TraceRange trace_range("dsce run calib");
     API_BEGIN
     check_ctx(ctx);
-    Scheme& s = bulk_export_check(ctx, id, out, flags, 0, "dsce_run_calib");
+    Scheme& s = bulk_export_check(ctx, id, out, flags, DSCE_LLR_PERFECT, "dsce_run_calib");
+    const bool perfect = (flags & DSCE_LLR_PERFECT) != 0;
+    if (perfect && out->ratio_perf0)
+        throw ApiError(DSCE_EINVAL, "dsce_run_calib: ratio_perf0 with DSCE_LLR_PERFECT (it is stage 0 of ratio_est)");
     const int ND = s.d.n_data, nsnr = ctx->nsnr, S = ctx->niter + 1;
     ExportSink sink{"dsce_run_calib", 2, {out->ratio_est, out->ratio_perf0}, {0, 0}, {sizeof(double), sizeof(double)},
                     false};
@@ -2980,12 +3005,11 @@ int dsce_run_calib(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep,
         q.acc_perf = out->ratio_perf0 ? acc + n_est : nullptr;
     }
     bulk_export(ctx, s, id, seed, first_rep, n_rep, sink, [&](const Bulk& bk, int snr0) {
-        q.k = llr_args(ctx, s, bk, snr0, false);
-        q.h = ctx->buf.h;
+        q.k = llr_args(ctx, s, bk, snr0, false, perfect);
         q.sidx = ctx->buf.sidx;
         Timed t(ctx, "k_llr_calib");
         launch_llr_calib(ctx->stream, q);
-    });
+    }, perfect);
     if (n_rep > 0 && !host.empty()) {
         DSCE_HIP_CHECK(hipMemcpyAsync(host.data(), q.acc_est ? q.acc_est : q.acc_perf, host.size() * sizeof(double),
                                       hipMemcpyDeviceToHost, ctx->stream));
@@ -3038,6 +3062,38 @@ int dsce_get_llr_scale(dsce_ctx* ctx, int32_t id, double* g_est, double* g_perf0
     }
     for (size_t i = 0; g_est && i < n_est; ++i) g_est[i] = s.g_est ? s.g_est_host[i] : 1.0;
     for (size_t i = 0; g_perf0 && i < n_perf; ++i) g_perf0[i] = s.g_perf0 ? s.g_perf0_host[i] : 1.0;
+    API_END
+}
+
+static int set_llr_scale_perf_one(dsce_ctx* ctx, int32_t id, const double* g_perf) {
+    API_BEGIN
+    check_ctx(ctx);
+    if (ctx->nsnr <= 0) throw ApiError(DSCE_ESTATE, "dsce_set_snr first");
+    Scheme& s = get_scheme(ctx, id);
+    const size_t n = (size_t)ctx->nsnr * (ctx->niter + 1) * s.d.n_data;
+    for (size_t i = 0; g_perf && i < n; ++i)
+        if (!(std::isfinite(g_perf[i]) && g_perf[i] > 0.0))
+            throw ApiError(DSCE_EINVAL, "dsce_set_llr_scale_perf: every entry must be finite and > 0");
+    drop_llr_scale_perf(ctx, s);
+    if (g_perf) {
+        s.g_perf_host.assign(g_perf, g_perf + n);
+        s.g_perf = dupload(ctx, s.g_perf_host);
+    }
+    API_END
+}
+
+int dsce_set_llr_scale_perf(dsce_ctx* ctx, int32_t id, const double* g_perf) {
+    return fanout(ctx, [&](dsce_ctx* c) { return set_llr_scale_perf_one(c, id, g_perf); });
+}
+
+int dsce_get_llr_scale_perf(dsce_ctx* ctx, int32_t id, double* g_perf, int32_t* set1) {
+    API_BEGIN
+    check_ctx(ctx);
+    if (ctx->nsnr <= 0) throw ApiError(DSCE_ESTATE, "dsce_set_snr first");
+    Scheme& s = get_scheme(ctx, id);
+    const size_t n = (size_t)ctx->nsnr * (ctx->niter + 1) * s.d.n_data;
+    if (set1) set1[0] = s.g_perf ? 1 : 0;
+    for (size_t i = 0; g_perf && i < n; ++i) g_perf[i] = s.g_perf ? s.g_perf_host[i] : 1.0;
     API_END
 }
 

@@ -82,7 +82,10 @@ struct TraceK {
     int unit;
     int LK, ND;
     double2* yest;     // y_est of stage s (the MMSE IC input y - (D_hat - diag) v), s >= 1
-    double2* yperf;    // y_perf of stage s (perfect-CSI IC), s >= 1; null: not wanted (bulk)
+    double2* yperf;    // y_perf of stage s (perfect-CSI IC), s >= 1; null: not wanted (bulk, unless
+                       // DSCE_LLR_PERFECT asks for it).  Bulk rows that are formed: the data rows on the
+                       // fused select paths (k_pic_fft, StorePerfectDetect: pilot rows and stage 0 stay
+                       // NaN), every row of stages >= 1 on the StorePerfectIC path (stage 0 stays NaN)
     double2* hest;     // diag(D_hat) of stage s
     int* dec_e;        // detected symbol index per data symbol, MMSE branch
     int* dec_p;        // perfect-CSI branch
@@ -150,6 +153,7 @@ struct McBuffers {
     double* mse_pow;  // [scheme][snr] sums of |h|^2
     const TraceK* tr; // device trace of one unit (null: not tracing this scheme / chunk)
     int tr_bulk;      // tr is in bulk mode (TraceK::U > 0): the launchers pick the bulk instances
+    int tr_yperf;     // ... and TraceK::yperf is non-null (DSCE_LLR_PERFECT): the instances that stage y_perf
 };
 
 struct MmseK {
@@ -326,11 +330,17 @@ struct LlrTab {
 // (k_llr; dsce_export_llr): from the bulk trace arrays y_ic / h_est
 // [stage][LK][U] the demapper input x_est, its noise power pn_eff and the m LLRs
 // of every data symbol, written [rep][snr][stage][ND]( [m]) like k_export_stages.
-// Fields in the order x_est (complex), pn_eff, llr (real).
+// Fields in the order x_est (complex), pn_eff, llr (real).  perfect
+// (DSCE_LLR_PERFECT): the perfect-CSI branch instead: stage s reads y_perf of
+// stage s (y = stage 0 of yic for s = 0) and the channel from h[l][rep]; only the
+// rows the demapper needs are read (data_pos, or P^H's columns), see TraceK::yperf.
 struct LlrK {
     LlrTab tab;
     const double2* yic;       // [S][LK][U]
     const double2* hest;      // [S][LK][U]
+    const double2* yperf;     // [S][LK][U] (stage 0 unused), or null unless perfect
+    const double2* h;         // [LK][R] perfect-CSI diag(D) of the batch (perfect, and the pseudo-stage)
+    int perfect;              // kernel-uniform: 1 = the perfect-CSI branch at every stage
     const double* pn;         // [nsnr] AWGN power per time sample
     const double* qn;         // [LK] ||Q[:, l]||^2
     const int* data_pos;      // select mode: ND rows
@@ -342,7 +352,8 @@ struct LlrK {
     int NP, LK, ND, S, R, U, snr0, nsnr, rvalid;
     long long row0;
     void* out[3];             // null: not requested
-    const double* scale;      // [nsnr][S][ND] pn_eff <- scale pn_eff (dsce_set_llr_scale), or null
+    const double* scale;      // [nsnr][S][ND] pn_eff <- scale pn_eff (dsce_set_llr_scale's g_est; perfect:
+                              // dsce_set_llr_scale_perf's g_perf), or null
 };
 void launch_llr(hipStream_t s, const LlrK& a, bool f32);
 // BICM information loss of one batch and SNR chunk after its last stage
@@ -350,7 +361,9 @@ void launch_llr(hipStream_t s, const LlrK& a, bool f32);
 // every stage, each LLR turned into loss_b = log2(1 + exp(-(2 t_b - 1) LLR_b))
 // with the transmitted bit t_b and summed instead of stored.  k: k_llr's
 // arguments (out and row0 unused).  Stage index S is the perfect-CSI one-tap
-// receiver: y = stage 0 of yic, the channel from h[l][rep] instead of hest.
+// receiver: y = stage 0 of yic, the channel from k.h[l][rep] instead of hest.
+// With k.perfect the stages 0 .. S - 1 are the perfect-CSI branch's (the pseudo-
+// stage is then stage 0 of acc_est and is not asked for).
 // One block = 64 units x one tile of LLR_INFO_LT data symbols of one stage; it
 // writes its pair of sums (all symbols, considered symbols) to slot
 // ((sc nst + st) nb + wave ntile + tile) of `part`, sc the SNR index in the
@@ -361,7 +374,6 @@ void launch_llr(hipStream_t s, const LlrK& a, bool f32);
 constexpr int LLR_INFO_LT = 64;
 struct LlrInfoK {
     LlrK k;
-    const double2* h;         // [LK][R] perfect-CSI diag(D) of the batch
     const uint16_t* sidx;     // [ND][R] transmitted symbol indices
     const int* considered;    // ND no-edge flags
     int st_lo, nst;           // stages [st_lo, st_lo + nst) of 0 .. S (S = the perfect-CSI one-tap receiver)
@@ -389,7 +401,6 @@ void launch_llr_info(hipStream_t s, const LlrInfoK& a);
 constexpr int LLR_CALIB_LT = 8;
 struct LlrCalibK {
     LlrK k;
-    const double2* h;         // [LK][R] perfect-CSI diag(D) of the batch
     const uint16_t* sidx;     // [ND][R] transmitted symbol indices
     int st_lo, nst;
     double* acc_est;          // [nsnr][S][ND], or null

@@ -1,6 +1,7 @@
 // kernels_llr.hip — soft outputs: SignalConstellation.LLR_AWGN
 // (SignalConstellation.m:103-122) as defined in include/dsce.h, for single points
 // (k_llr_probe; dsce_llr_awgn) and in bulk for every stage of the MMSE branch
+// or of the perfect-CSI branch (LlrK::perfect; DSCE_LLR_PERFECT)
 // (k_llr; dsce_export_llr), and the BICM information loss summed from those LLRs
 // on the device (k_llr_info + k_llr_info_sum; dsce_run_soft).  One device
 // function, llr_demap, serves all of them.  k_llr_calib (dsce_run_calib) sums the
@@ -171,13 +172,14 @@ void launch_llr_probe(hipStream_t s, const LlrTab& t, const double2* x, const do
 }
 
 // The demapper input of data symbol j for the lane's unit, as include/dsce.h
-// defines it: x_est and the AWGN pn_eff from row(s) base + l of y [..][U] at
-// `unit` and of h [..][hU] at `hunit` (h_est of the stage, or the batch's
-// perfect-CSI diag(D) for the pseudo-stage).  One statement sequence for k_llr,
-// k_llr_info and k_llr_calib, so the three form the same bits.
-__device__ __forceinline__ void llr_input(const LlrK& a, const double2* __restrict__ hsrc, size_t base, size_t U,
-                                          size_t unit, size_t hU, size_t hunit, int j, double pnk, double2& x,
-                                          double& pe) {
+// defines it: x_est and the AWGN pn_eff from row(s) base + l of ysrc [..][U] at
+// `unit` and row(s) hbase + l of hsrc [..][hU] at `hunit` (y_ic and h_est of the
+// stage; or y_perf of the stage, y for stage 0 and the pseudo-stage, with the
+// batch's perfect-CSI diag(D): LlrSrc below).  One statement sequence for k_llr,
+// k_llr_info and k_llr_calib and for both branches, so all form the same bits.
+__device__ __forceinline__ void llr_input(const LlrK& a, const double2* __restrict__ ysrc, size_t base, size_t U,
+                                          size_t unit, const double2* __restrict__ hsrc, size_t hbase, size_t hU,
+                                          size_t hunit, int j, double pnk, double2& x, double& pe) {
     if (a.despread) {                                      // x = P^H (y ./ h), row NP + j of P^H
         double2 acc = make_double2(0.0, 0.0);
         double pacc = 0.0;
@@ -185,7 +187,7 @@ __device__ __forceinline__ void llr_input(const LlrK& a, const double2* __restri
         for (int jj = j0; jj < j1; ++jj) {
             const int l = a.ph_col[jj];
             const double2 pv = a.ph_val[jj];
-            const double2 y = a.yic[(base + l) * U + unit], h = hsrc[(base + l) * hU + hunit];
+            const double2 y = ysrc[(base + l) * U + unit], h = hsrc[(hbase + l) * hU + hunit];
             c_fma(acc, pv, c_div(y, h));
             pacc += (pv.x * pv.x + pv.y * pv.y) * (pnk * a.qn[l]) / (h.x * h.x + h.y * h.y);
         }
@@ -193,12 +195,34 @@ __device__ __forceinline__ void llr_input(const LlrK& a, const double2* __restri
         pe = pacc / (a.data_div * a.data_div);
     } else {
         const int l = a.data_pos[j];
-        const double2 y = a.yic[(base + l) * U + unit], h = hsrc[(base + l) * hU + hunit];
+        const double2 y = ysrc[(base + l) * U + unit], h = hsrc[(hbase + l) * hU + hunit];
         const double2 q = c_div(y, h);
         x = make_double2(q.x / a.data_div, q.y / a.data_div);
         pe = pnk * a.qn[l] / ((h.x * h.x + h.y * h.y) * (a.data_div * a.data_div));
     }
     if (a.real_detect) x.y = 0.0;
+}
+
+// Where stage `stage` of 0 .. S reads its observation and its channel (block-
+// uniform).  MMSE branch: y_ic and h_est of the stage, [S][LK][U].  Perfect CSI
+// (the pseudo-stage S, or every stage with LlrK::perfect): y_perf of the stage,
+// y = stage 0 of y_ic for stage 0 and the pseudo-stage, and diag(D) h[l][rep].
+struct LlrSrc {
+    const double2* y;
+    const double2* h;
+    size_t base, hbase, hU;
+    bool perf;
+};
+__device__ __forceinline__ LlrSrc llr_src(const LlrK& a, int stage) {
+    LlrSrc r;
+    const bool pseudo = stage == a.S;
+    r.perf = pseudo || a.perfect != 0;
+    r.y = (r.perf && !pseudo && stage > 0) ? a.yperf : a.yic;
+    r.base = pseudo ? 0 : (size_t)stage * a.LK;
+    r.h = r.perf ? a.h : a.hest;
+    r.hbase = r.perf ? 0 : r.base;
+    r.hU = r.perf ? (size_t)a.R : (size_t)a.U;
+    return r;
 }
 
 // k_llr — the sibling of k_export_stages for the soft outputs.  One block = 64
@@ -228,7 +252,8 @@ __global__ void __launch_bounds__(256) k_llr(LlrK a) {
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const size_t U = (size_t)a.U, unit = (size_t)first + lane;
-    const size_t base = (size_t)stage * a.LK;
+    const LlrSrc sr = llr_src(a, stage);
+    const size_t hunit = sr.perf ? (size_t)(rl0 + lane) : unit;
     const double pnk = a.pn[snr];
     const bool want_llr = a.out[2] != nullptr;
     for (int e = w; e < LT; e += 4) {
@@ -236,7 +261,7 @@ __global__ void __launch_bounds__(256) k_llr(LlrK a) {
         if (j >= a.ND) break;                              // wave-uniform
         double2 x;
         double pe;
-        llr_input(a, a.hest, base, U, unit, U, unit, j, pnk, x, pe);
+        llr_input(a, sr.y, sr.base, U, unit, sr.h, sr.hbase, sr.hU, hunit, j, pnk, x, pe);
         if (a.scale) pe = a.scale[((size_t)snr * a.S + stage) * a.ND + j] * pe;   // wave-uniform load
         xt[lane * XS + e] = x;
         pt[lane * XS + e] = pe;
@@ -317,7 +342,7 @@ __global__ void __launch_bounds__(256) k_llr_info(LlrInfoK q) {
     const int ntile = (a.ND + LT - 1) / LT;
     const int st = blockIdx.y / ntile, tile = blockIdx.y % ntile, e0 = tile * LT;
     const int stage = q.st_lo + st;
-    const bool perf = stage == a.S;                        // the perfect-CSI one-tap receiver
+    const bool pseudo = stage == a.S;                      // the perfect-CSI one-tap receiver
     const int first = blockIdx.x * 64;                     // first unit of the block (one SNR point: R % 64 == 0)
     const int sc = first / a.R, snr = a.snr0 + sc;
     const int rl0 = first % a.R;
@@ -326,12 +351,11 @@ __global__ void __launch_bounds__(256) k_llr_info(LlrInfoK q) {
     const int rep = rl0 + lane;
     const bool counts = rep < a.rvalid;                    // a padding realisation adds nothing
     const size_t U = (size_t)a.U, unit = (size_t)first + lane;
-    const size_t base = perf ? 0 : (size_t)stage * a.LK;   // perfect CSI: y = stage 0 of y_ic
-    const double2* hsrc = perf ? q.h : a.hest;
-    const size_t hU = perf ? (size_t)a.R : U, hunit = perf ? (size_t)rep : unit;
+    const LlrSrc sr = llr_src(a, stage);
+    const size_t hunit = sr.perf ? (size_t)rep : unit;
     const double pnk = a.pn[snr];
-    // the scale row of (snr, stage): dsce_set_llr_scale's g_est, g_perf0 for the pseudo-stage
-    const double* scale = perf ? (q.scale_perf ? q.scale_perf + (size_t)snr * a.ND : nullptr)
+    // the scale row of (snr, stage): a.scale (g_est, or g_perf of the perfect-CSI branch), g_perf0 for the pseudo-stage
+    const double* scale = pseudo ? (q.scale_perf ? q.scale_perf + (size_t)snr * a.ND : nullptr)
                                : (a.scale ? a.scale + ((size_t)snr * a.S + stage) * a.ND : nullptr);
     double sum_all = 0.0, sum_con = 0.0;
     if (rl0 < a.rvalid)                                    // else a wave of tail padding (block-uniform)
@@ -340,7 +364,7 @@ __global__ void __launch_bounds__(256) k_llr_info(LlrInfoK q) {
             if (j >= a.ND) break;                          // wave-uniform
             double2 x;
             double pe;
-            llr_input(a, hsrc, base, U, unit, hU, hunit, j, pnk, x, pe);
+            llr_input(a, sr.y, sr.base, U, unit, sr.h, sr.hbase, sr.hU, hunit, j, pnk, x, pe);
             if (scale) pe = scale[j] * pe;                 // wave-uniform load
             const unsigned t = q.sidx[(size_t)j * a.R + rep];
             double sym = 0.0;
@@ -404,14 +428,12 @@ __global__ void __launch_bounds__(256) k_llr_calib(LlrCalibK q) {
     const int ntile = (a.ND + LT - 1) / LT;
     const int st = blockIdx.y / ntile, e0 = (blockIdx.y % ntile) * LT;
     const int stage = q.st_lo + st;
-    const bool perf = stage == a.S;                        // the perfect-CSI one-tap receiver
+    const bool pseudo = stage == a.S;                      // the perfect-CSI one-tap receiver
     const int sc = blockIdx.x, snr = a.snr0 + sc;          // SNR point of the chunk
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const size_t U = (size_t)a.U;
-    const size_t base = perf ? 0 : (size_t)stage * a.LK;   // perfect CSI: y = stage 0 of y_ic
-    const double2* hsrc = perf ? q.h : a.hest;
-    const size_t hU = perf ? (size_t)a.R : U;
+    const LlrSrc sr = llr_src(a, stage);
     const double pnk = a.pn[snr];
     const double c = a.real_detect ? 2.0 : 1.0;            // a real observation has variance pn_eff / 2
     double sum[PER];
@@ -421,14 +443,14 @@ __global__ void __launch_bounds__(256) k_llr_calib(LlrCalibK q) {
         const int rep = rl0 + lane;
         const bool counts = rep < a.rvalid;                // a padding realisation adds nothing
         const size_t unit = (size_t)sc * a.R + rep;
-        const size_t hunit = perf ? (size_t)rep : unit;
+        const size_t hunit = sr.perf ? (size_t)rep : unit;
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
             const int j = e0 + w + 4 * i;
             if (j >= a.ND) break;                          // wave-uniform
             double2 x;
             double pe;
-            llr_input(a, hsrc, base, U, unit, hU, hunit, j, pnk, x, pe);
+            llr_input(a, sr.y, sr.base, U, unit, sr.h, sr.hbase, sr.hU, hunit, j, pnk, x, pe);
             const unsigned t = counts ? q.sidx[(size_t)j * a.R + rep] : 0u;
             const double2 s = a.tab.symbols[t];
             const double dx = x.x - s.x, dy = a.real_detect ? 0.0 : x.y - s.y;
@@ -443,7 +465,7 @@ __global__ void __launch_bounds__(256) k_llr_calib(LlrCalibK q) {
         for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
         const int j = e0 + w + 4 * i;
         if (lane == 0 && j < a.ND) {
-            double* dst = perf ? q.acc_perf + (size_t)snr * a.ND + j : q.acc_est + ((size_t)snr * a.S + stage) * a.ND + j;
+            double* dst = pseudo ? q.acc_perf + (size_t)snr * a.ND + j : q.acc_est + ((size_t)snr * a.S + stage) * a.ND + j;
             *dst += v;
         }
     }

@@ -1241,9 +1241,11 @@ struct StorePerfectDetect {
         c0 = 0;
         c1 = 0;
     }
-    // BULK (the methods' last template argument): TraceK's bulk mode, every unit
+    // BULK (a template argument of the methods): TraceK's bulk mode, every unit
     // stores; StorePerfectDetectBulk below calls those forms, so a kernel has one
-    // instance per mode and the instance dsce_run launches keeps its code
+    // instance per mode and the instance dsce_run launches keeps its code.  YPERF:
+    // the bulk mode also stages y_perf (DSCE_LLR_PERFECT; StorePerfectDetectBulkY),
+    // again an instance of its own, so the unflagged bulk exports keep theirs
     __device__ __forceinline__ void operator()(int row, int lane, double2 acc) {
         if (row_data[row] < 0) return;
         detect(row, lane, acc, u[(size_t)row * U + lane]);
@@ -1261,7 +1263,7 @@ struct StorePerfectDetect {
                                            const double2 (&ur)[RBN]) {
         rows_impl<RBN, true>(row0, nrows, lane, acc, ur);
     }
-    template <int RBN, bool UREG, bool BULK = false>
+    template <int RBN, bool UREG, bool BULK = false, bool YPERF = false>
     __device__ __forceinline__ void rows_impl(int row0, int nrows, int lane, const double2 (&acc)[RBN],
                                               const double2 (&ur)[RBN]) {
         const int rl = lane % R;
@@ -1295,7 +1297,8 @@ struct StorePerfectDetect {
                 c0 += ne;
                 c1 += cn[k] ? ne : 0;
                 if (tr && trace_hit<BULK>(tr, lane)) {
-                    if constexpr (!BULK) tr->yperf[(size_t)stage * tr->LK + row0 + r] = rr;   // not exported in bulk
+                    if constexpr (!BULK) tr->yperf[(size_t)stage * tr->LK + row0 + r] = rr;
+                    else if constexpr (YPERF) tr->yperf[trace_ix<BULK>(tr, (size_t)stage * tr->LK + row0 + r, lane)] = rr;
                     tr->dec_p[trace_ix<BULK>(tr, (size_t)stage * tr->ND + dd[k], lane)] = dp;
                 }
                 if (!last) {
@@ -1307,7 +1310,7 @@ struct StorePerfectDetect {
         }
     }
     // y_perf = y - acc + h u of one row, sliced, counted, re-precoded into u
-    template <bool BULK = false>
+    template <bool BULK = false, bool YPERF = false>
     __device__ __forceinline__ void detect(int row, int lane, double2 acc, double2 uv) {
         const size_t i = (size_t)row * U + lane;
         const int rl = lane % R;
@@ -1324,6 +1327,7 @@ struct StorePerfectDetect {
         c1 += row_cons[row] ? ne : 0;
         if (tr && trace_hit<BULK>(tr, lane)) {
             if constexpr (!BULK) tr->yperf[(size_t)stage * tr->LK + row] = r;
+            else if constexpr (YPERF) tr->yperf[trace_ix<BULK>(tr, (size_t)stage * tr->LK + row, lane)] = r;
             tr->dec_p[trace_ix<BULK>(tr, (size_t)stage * tr->ND + d, lane)] = dp;
         }
         if (!last) {
@@ -1362,6 +1366,24 @@ struct StorePerfectDetectBulk : StorePerfectDetect {
     __device__ __forceinline__ void rows_u(int row0, int nrows, int lane, const double2 (&acc)[RBN],
                                            const double2 (&ur)[RBN]) {
         rows_impl<RBN, true, true>(row0, nrows, lane, acc, ur);
+    }
+};
+// ... and with y_perf staged too: tr->yperf [stage][LK][U] is non-null (DSCE_LLR_PERFECT)
+struct StorePerfectDetectBulkY : StorePerfectDetect {
+    StorePerfectDetectBulkY() = default;
+    __host__ __device__ StorePerfectDetectBulkY(const StorePerfectDetect& o) : StorePerfectDetect(o) {}
+    __device__ __forceinline__ void operator()(int row, int lane, double2 acc) {
+        if (row_data[row] < 0) return;
+        detect<true, true>(row, lane, acc, u[(size_t)row * U + lane]);
+    }
+    template <int RBN>
+    __device__ __forceinline__ void rows(int row0, int nrows, int lane, const double2 (&acc)[RBN]) {
+        rows_impl<RBN, false, true, true>(row0, nrows, lane, acc, acc);
+    }
+    template <int RBN>
+    __device__ __forceinline__ void rows_u(int row0, int nrows, int lane, const double2 (&acc)[RBN],
+                                           const double2 (&ur)[RBN]) {
+        rows_impl<RBN, true, true, true>(row0, nrows, lane, acc, ur);
     }
 };
 
@@ -3607,12 +3629,15 @@ unsigned launch_perfect_ic(hipStream_t s, const Opts& op, const SchemeK& sk, con
     o.stage = pd->stage;
     const size_t lds = 256 * sizeof(double2) + sizeof(SlicerLds);
     const bool bulk = b.tr && b.tr_bulk;
+    const bool bulk_y = bulk && b.tr_yperf;               // ... and y_perf is staged (DSCE_LLR_PERFECT)
     if (poly) {
-        if (bulk) launch_poly_ana(s, sk, pa, StorePerfectDetectBulk(o), lds);
+        if (bulk_y) launch_poly_ana(s, sk, pa, StorePerfectDetectBulkY(o), lds);
+        else if (bulk) launch_poly_ana(s, sk, pa, StorePerfectDetectBulk(o), lds);
         else launch_poly_ana(s, sk, pa, o, lds);
         return PATH_PIC_POLY;
     }
-    if (bulk) launch_pass2_nt(s, sk, ch, b, ord, StorePerfectDetectBulk(o), lds);
+    if (bulk_y) launch_pass2_nt(s, sk, ch, b, ord, StorePerfectDetectBulkY(o), lds);
+    else if (bulk) launch_pass2_nt(s, sk, ch, b, ord, StorePerfectDetectBulk(o), lds);
     else launch_pass2_nt(s, sk, ch, b, ord, o, lds);
     return PATH_PIC_PASSES;
 }

@@ -28,7 +28,10 @@ the metadata.  bit_errors(sym, dec) counts their bit errors per (SNR, stage).
 (dsce_export_llr; the stage settings of --stages, --n-iter): the demapper input
 x_est [n][n_snr][S][ND], its noise power pn_eff (same shape, float32 / float64)
 and llr [n][n_snr][S][ND][m], positive = bit 1, and llr_method and n_iter in the
-metadata."""
+metadata.  --llr-branch mmse|perfect|both (default mmse) chooses the branch:
+the perfect-CSI arrays (DSCE_LLR_PERFECT: y_perf of the stage over the true
+one-tap channel h) are stored as x_perf, pn_perf and llr_perf, and llr_branch
+goes into the metadata."""
 from __future__ import annotations
 
 import argparse
@@ -46,6 +49,10 @@ STAGE_NAMES = {"hp_ls": "hp_ls_stages", "h_est": "h_est_stages", "y_ic": "y_ic_s
 STAGE_ARRAYS = tuple(STAGE_NAMES.values())
 # dsce_export_llr fields (--llr), under their own names; the method is metadata key "llr_method"
 LLR_ARRAYS = ("x_est", "pn_eff", "llr")
+# shard name of each dsce_export_llr field of the perfect-CSI branch (--llr-branch perfect | both)
+LLR_PERF_NAMES = {"x_est": "x_perf", "pn_eff": "pn_perf", "llr": "llr_perf"}
+LLR_PERF_ARRAYS = tuple(LLR_PERF_NAMES.values())
+LLR_BRANCHES = ("mmse", "perfect", "both")
 
 
 def bit_errors(sym, dec, considered=None):
@@ -87,7 +94,7 @@ def write_shard(path, arrays, meta):
     file, then os.replace).  meta must carry first_rep and n_rep."""
     n = int(meta["n_rep"])
     for k, a in arrays.items():
-        if k not in FIELDS and k not in STAGE_ARRAYS and k not in LLR_ARRAYS:
+        if k not in FIELDS and k not in STAGE_ARRAYS and k not in LLR_ARRAYS and k not in LLR_PERF_ARRAYS:
             raise ValueError("unknown field %r" % k)
         if a.shape[0] != n:
             raise ValueError("field %s holds %d realisations, the shard %d" % (k, a.shape[0], n))
@@ -150,6 +157,9 @@ def parser():
                     help="add the per-stage IC arrays (hp_ls_stages, h_est_stages, y_ic_stages, dec_est, dec_perf)")
     ap.add_argument("--llr", choices=("exact", "maxlog"), default=None,
                     help="add the soft outputs of the MMSE branch per stage (x_est, pn_eff, llr)")
+    ap.add_argument("--llr-branch", choices=LLR_BRANCHES, default="mmse",
+                    help="with --llr: the MMSE branch (x_est, pn_eff, llr), the perfect-CSI branch "
+                         "(x_perf, pn_perf, llr_perf) or both")
     ap.add_argument("--n-iter", type=int, default=None, help="IC iterations of --stages / --llr (default 4)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", required=True, help="shard prefix: writes PREFIX-00000.npz ...")
@@ -165,6 +175,8 @@ def main(argv=None):
         raise SystemExit("--n-iter belongs to --stages / --llr")
     if staged and a.no_mmse:
         raise SystemExit("--stages / --llr need the MMSE estimator (drop --no-mmse)")
+    if a.llr_branch != "mmse" and a.llr is None:
+        raise SystemExit("--llr-branch belongs to --llr")
     if a.n_iter is not None and a.n_iter < 0:
         raise SystemExit("--n-iter must be >= 0")
 
@@ -185,14 +197,19 @@ def main(argv=None):
         base["n_iter"] = int(S.n_iter)
     if a.llr is not None:
         base["llr_method"] = a.llr
+        if a.llr_branch != "mmse":
+            base["llr_branch"] = a.llr_branch
     try:
         for i, (first, n) in enumerate(shard_ranges(a.first_rep, a.reps, a.shard_reps)):
             arrays = eng.export(0, a.seed, first, n, fields=fields, dtype=np.dtype(a.dtype))
             if a.stages:
                 st = eng.export_stages(0, a.seed, first, n, dtype=np.dtype(a.dtype))
                 arrays.update({STAGE_NAMES[f]: v for f, v in st.items()})
-            if a.llr is not None:
+            if a.llr is not None and a.llr_branch in ("mmse", "both"):
                 arrays.update(eng.export_llr(0, a.seed, first, n, method=a.llr, dtype=np.dtype(a.dtype)))
+            if a.llr is not None and a.llr_branch in ("perfect", "both"):
+                pf = eng.export_llr(0, a.seed, first, n, method=a.llr, dtype=np.dtype(a.dtype), branch="perfect")
+                arrays.update({LLR_PERF_NAMES[f]: v for f, v in pf.items()})
             print("wrote", write_shard(shard_path(a.out, i), arrays, dict(base, first_rep=int(first), n_rep=int(n))),
                   flush=True)
     finally:

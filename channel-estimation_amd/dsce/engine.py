@@ -29,6 +29,7 @@ EXPORTED = [
     "dsce_transmission_matrix", "dsce_jakes_info", "dsce_export", "dsce_export_stages",
     "dsce_llr_awgn", "dsce_export_llr", "dsce_llr_info", "dsce_run_soft",
     "dsce_run_calib", "dsce_set_llr_scale", "dsce_get_llr_scale",
+    "dsce_set_llr_scale_perf", "dsce_get_llr_scale_perf",
 ]
 
 ABI_VERSION = 10
@@ -45,6 +46,9 @@ LLR_MAXLOG = 1 << 2
 # dsce_export_llr fields in the order of dsce_export_llr_out
 LLR_FIELDS = ("x_est", "pn_eff", "llr")
 LLR_METHODS = {"exact": 0, "maxlog": LLR_MAXLOG}
+# the perfect-CSI branch of export_llr / run_soft / run_calib (DSCE_LLR_PERFECT; DSCE_HAS_LLR_PERFECT)
+LLR_PERFECT = 1 << 4
+LLR_BRANCHES = {"mmse": 0, "perfect": LLR_PERFECT}
 
 # dsce_jakes_info kernels (include/dsce.h DSCE_JAKES_*)
 JAKES_KERNELS = {0: "none", 1: "static", 2: "discrete", 3: "full", 4: "win_rec", 5: "win_mom", 6: "win_grp"}
@@ -187,6 +191,8 @@ def load_library(path=None):
     lib.dsce_run_calib.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(CalibOut)]
     lib.dsce_set_llr_scale.argtypes = [vp, C.c_int32, dp, dp]
     lib.dsce_get_llr_scale.argtypes = [vp, C.c_int32, dp, dp, C.POINTER(C.c_int32)]
+    lib.dsce_set_llr_scale_perf.argtypes = [vp, C.c_int32, dp]
+    lib.dsce_get_llr_scale_perf.argtypes = [vp, C.c_int32, dp, C.POINTER(C.c_int32)]
     for name in EXPORTED:
         fn = getattr(lib, name)
         if name != "dsce_last_error":
@@ -430,14 +436,14 @@ class Engine:
     _export_stages = functools.partialmethod(_export_call, "stages")
     _export_llr = functools.partialmethod(_export_call, "llr")
 
-    def _bulk_export(self, kind, sid, seed, first_rep, n_rep, fields, arrays, method=None):
+    def _bulk_export(self, kind, sid, seed, first_rep, n_rep, fields, arrays, method=None, branch="mmse"):
         """Export `kind` into arrays that `arrays` (_HostArrays or _TorchArrays)
         allocates: a dict field -> array."""
         k = _EXPORTS[kind]
         shapes = k.shapes(self, sid, n_rep)
         out = {f: arrays.empty(shapes[f], k.kinds[f]) for f in fields}
         arrays.ready()
-        flags = arrays.flags | (0 if method is None else self._llr_flag(method))
+        flags = arrays.flags | (0 if method is None else self._llr_flag(method)) | self._branch_flag(branch)
         self._export_call(kind, sid, seed, first_rep, n_rep, flags, {f: arrays.address(a) for f, a in out.items()})
         return out
 
@@ -505,6 +511,12 @@ class Engine:
             raise ValueError("LLR method must be 'exact' or 'maxlog'")
         return LLR_METHODS[method]
 
+    @staticmethod
+    def _branch_flag(branch):
+        if branch not in LLR_BRANCHES:
+            raise ValueError("branch must be 'mmse' or 'perfect'")
+        return LLR_BRANCHES[branch]
+
     def llr_info(self, sid):
         """dict(per_axis, m) of scheme sid's demapper (dsce_llr_info): per_axis =
         every bit of the label depends on one axis of the constellation grid, so
@@ -532,24 +544,26 @@ class Engine:
         base = (n, d.n_snr, S, d.n_data)
         return dict(x_est=base, pn_eff=base, llr=base + (self.llr_info(sid)["m"],))
 
-    def export_llr(self, sid, seed, first_rep, n_rep, fields=LLR_FIELDS, method="exact", dtype=np.complex128):
-        """Soft outputs of the MMSE branch for realisations [first_rep, first_rep +
+    def export_llr(self, sid, seed, first_rep, n_rep, fields=LLR_FIELDS, method="exact", dtype=np.complex128,
+                   branch="mmse"):
+        """Soft outputs of the MMSE branch (branch 'perfect': of the perfect-CSI
+        branch, DSCE_LLR_PERFECT: y_perf of the stage over h = diag(D)) for realisations [first_rep, first_rep +
         n_rep) of scheme sid, every SNR point and stage (dsce_export_llr) as a dict
         of NumPy arrays: the demapper input x_est [n_rep][n_snr][S][ND] (dtype
         complex128, or complex64: DSCE_EXPORT_F32), its noise power pn_eff (same
         shape, float64 / float32) and llr [n_rep][n_snr][S][ND][m], positive = bit
         1, method 'exact' (log-sum-exp) or 'maxlog'.  Realisation rep is
         realisation rep of run(), export() and export_stages() with the same seed."""
-        return self._bulk_export("llr", sid, seed, first_rep, n_rep, fields, _HostArrays(dtype), method)
+        return self._bulk_export("llr", sid, seed, first_rep, n_rep, fields, _HostArrays(dtype), method, branch)
 
     def export_llr_torch(self, sid, seed, first_rep, n_rep, fields=LLR_FIELDS, method="exact", dtype=None,
-                         device=None):
+                         device=None, branch="mmse"):
         """export_llr() into torch tensors on the context's GPU, written by the
         kernel itself (DSCE_EXPORT_DEVICE); dtype torch.complex128 (x_est; pn_eff
         and llr float64) or torch.complex64 (float32).  See export_torch for
         device and the import order of torch and the engine."""
         return self._bulk_export("llr", sid, seed, first_rep, n_rep, fields,
-                                 _TorchArrays(self, "export_llr_torch", dtype, device), method)
+                                 _TorchArrays(self, "export_llr_torch", dtype, device), method, branch)
 
     # -- BICM rate from the LLRs (DSCE_HAS_SOFT_RUN) --------------------------------
     def soft_shapes(self, sid):
@@ -557,7 +571,7 @@ class Engine:
         d = self.scheme_dims(sid)
         return dict(loss_est=(d.n_snr, d.n_iter + 1, 2), loss_perf0=(d.n_snr, 2))
 
-    def run_soft(self, sid, seed, first_rep, n_rep, method="exact", out=None):
+    def run_soft(self, sid, seed, first_rep, n_rep, method="exact", out=None, branch="mmse"):
         """Information loss of the LLRs that export_llr would return for realisations
         [first_rep, first_rep + n_rep) of scheme sid, summed on the GPU
         (dsce_run_soft): dict of float64 arrays loss_est [n_snr][S][2] (MMSE branch,
@@ -567,10 +581,12 @@ class Engine:
         dsce.modulation.bicm_info_loss).  The sums are ADDED into the arrays of
         `out` (a dict with either or both keys, C-contiguous float64; only the
         given ones are computed) and `out` is returned; without it both are
-        computed from zero.  bicm_rate turns a sum into a rate."""
+        computed from zero.  bicm_rate turns a sum into a rate.  branch 'perfect'
+        (DSCE_LLR_PERFECT): loss_est receives the sums of the perfect-CSI branch at
+        every stage, and loss_perf0 (its stage 0) may not be given."""
         shapes = self.soft_shapes(sid)
         if out is None:
-            out = {f: np.zeros(shp) for f, shp in shapes.items()}
+            out = {f: np.zeros(shp) for f, shp in shapes.items() if branch == "mmse" or f == "loss_est"}
         o = SoftOut()
         for f, a in out.items():
             if f not in shapes:
@@ -580,7 +596,8 @@ class Engine:
                 raise ValueError("%s must be a C-contiguous float64 array of shape %s" % (f, shapes[f]))
             setattr(o, f, _dptr(a))
         self._chk(self.lib.dsce_run_soft(self.h, int(sid), int(seed), int(first_rep), int(n_rep),
-                                         self._llr_flag(method), C.byref(o)), "dsce_run_soft")
+                                         self._llr_flag(method) | self._branch_flag(branch), C.byref(o)),
+                  "dsce_run_soft")
         return out
 
     def bicm_rate(self, sid, loss, n_rep):
@@ -599,7 +616,7 @@ class Engine:
         d = self.scheme_dims(sid)
         return dict(ratio_est=(d.n_snr, d.n_iter + 1, d.n_data), ratio_perf0=(d.n_snr, d.n_data))
 
-    def run_calib(self, sid, seed, first_rep, n_rep, out=None):
+    def run_calib(self, sid, seed, first_rep, n_rep, out=None, branch="mmse"):
         """Demapper noise ratio of realisations [first_rep, first_rep + n_rep) of
         scheme sid, summed on the GPU (dsce_run_calib): dict of float64 arrays
         ratio_est [n_snr][S][ND] (MMSE branch, per stage and data symbol) and
@@ -608,10 +625,12 @@ class Engine:
         (dsce.modulation.demapper_noise_ratio); rho = ratio / n_rep is what
         set_llr_scale takes.  The sums are ADDED into the arrays of `out` (a dict
         with either or both keys, C-contiguous float64; only the given ones are
-        computed) and `out` is returned; without it both are computed from zero."""
+        computed) and `out` is returned; without it both are computed from zero.
+        branch 'perfect' (DSCE_LLR_PERFECT): ratio_est is the perfect-CSI branch's at
+        every stage (rho for set_llr_scale_perf), and ratio_perf0 may not be given."""
         shapes = self.calib_shapes(sid)
         if out is None:
-            out = {f: np.zeros(shp) for f, shp in shapes.items()}
+            out = {f: np.zeros(shp) for f, shp in shapes.items() if branch == "mmse" or f == "ratio_est"}
         o = CalibOut()
         for f, a in out.items():
             if f not in shapes:
@@ -620,8 +639,8 @@ class Engine:
                     and a.shape == shapes[f]):
                 raise ValueError("%s must be a C-contiguous float64 array of shape %s" % (f, shapes[f]))
             setattr(o, f, _dptr(a))
-        self._chk(self.lib.dsce_run_calib(self.h, int(sid), int(seed), int(first_rep), int(n_rep), 0, C.byref(o)),
-                  "dsce_run_calib")
+        self._chk(self.lib.dsce_run_calib(self.h, int(sid), int(seed), int(first_rep), int(n_rep),
+                                          self._branch_flag(branch), C.byref(o)), "dsce_run_calib")
         return out
 
     def set_llr_scale(self, sid, g_est=None, g_perf0=None):
@@ -651,6 +670,27 @@ class Engine:
         self._chk(self.lib.dsce_get_llr_scale(self.h, int(sid), _dptr(g_est), _dptr(g_perf0), set2),
                   "dsce_get_llr_scale")
         return dict(g_est=g_est, g_perf0=g_perf0, set=(bool(set2[0]), bool(set2[1])))
+
+    def set_llr_scale_perf(self, sid, g_perf=None):
+        """Install the scale table of the branch='perfect' calls of scheme sid
+        (dsce_set_llr_scale_perf): g_perf [n_snr][S][ND] multiplies pn_eff in the
+        flagged export_llr and run_soft; None removes it.  Every entry finite and
+        > 0.  set_snr drops the table; the unflagged calls never read it."""
+        if g_perf is not None:
+            g_perf = np.ascontiguousarray(g_perf, dtype=np.float64)
+            shape = self.calib_shapes(sid)["ratio_est"]
+            if g_perf.shape != shape:
+                raise ValueError("scale table must have shape %s" % (shape,))
+        self._chk(self.lib.dsce_set_llr_scale_perf(self.h, int(sid), None if g_perf is None else _dptr(g_perf)),
+                  "dsce_set_llr_scale_perf")
+
+    def llr_scale_perf(self, sid):
+        """dict(g_perf, set) of scheme sid (dsce_get_llr_scale_perf): the installed
+        table (ones where none is installed) and set = bool."""
+        g_perf = np.zeros(self.calib_shapes(sid)["ratio_est"])
+        set1 = (C.c_int32 * 1)()
+        self._chk(self.lib.dsce_get_llr_scale_perf(self.h, int(sid), _dptr(g_perf), set1), "dsce_get_llr_scale_perf")
+        return dict(g_perf=g_perf, set=bool(set1[0]))
 
     # -- engine state ------------------------------------------------------------
     def scheme_dims(self, sid):

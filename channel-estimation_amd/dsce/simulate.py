@@ -66,7 +66,8 @@ def main(argv=None):
                          "(exact, or max-log: the mismatched-decoder rate), summed on the GPU (dsce_run_soft)")
     ap.add_argument("--calibrate", action="store_true",
                     help="with --rate: measure the demapper noise ratio rho per SNR point, stage and data symbol "
-                         "over the same realisations (dsce_run_calib), scale pn_eff by it (dsce_set_llr_scale) and "
+                         "over the same realisations (dsce_run_calib), for the MMSE and the perfect-CSI branch, "
+                         "scale pn_eff by it (dsce_set_llr_scale, dsce_set_llr_scale_perf) and "
                          "report the rate of the scaled LLRs too.  rho is in-sample: the calibrated rate is biased "
                          "upward by O(1 / reps), so a sweep wants thousands of realisations")
     a = ap.parse_args(argv)
@@ -132,12 +133,15 @@ def main(argv=None):
     pw = np.zeros((len(names), nsnr))
     loss_e = np.zeros((len(names), nsnr, nst, 2))
     loss_p = np.zeros((len(names), nsnr, 2))
+    loss_pi = np.zeros_like(loss_e)                  # the perfect-CSI branch at every stage (DSCE_LLR_PERFECT)
     bits, rate_s = None, 0.0
     # --calibrate: the ratio sums and the losses of the scaled LLRs
     n_data = [int(S.schemes[s].n_data) for s in names]
     ratio_e = [np.zeros((nsnr, nst, nd)) for nd in n_data]
     ratio_p = [np.zeros((nsnr, nd)) for nd in n_data]
     closs_e, closs_p = np.zeros_like(loss_e), np.zeros_like(loss_p)
+    ratio_pi = [np.zeros((nsnr, nst, nd)) for nd in n_data]
+    closs_pi = np.zeros_like(loss_e)
     eng = None
     setup_s, t0 = 0.0, time.perf_counter()
     ck_path = None
@@ -193,11 +197,18 @@ def main(argv=None):
                 out = {"loss_est": loss_e[i], "loss_perf0": loss_p[i]}
                 for at in range(0, mine, step):
                     eng.run_soft(i, a.seed, first + at, min(step, mine - at), a.rate, out)
+                # one more pass for the perfect-CSI branch
+                out = {"loss_est": loss_pi[i]}
+                for at in range(0, mine, step):
+                    eng.run_soft(i, a.seed, first + at, min(step, mine - at), a.rate, out, branch="perfect")
             if a.calibrate:
                 for i in range(len(names)):
                     out = {"ratio_est": ratio_e[i], "ratio_perf0": ratio_p[i]}
                     for at in range(0, mine, step):
                         eng.run_calib(i, a.seed, first + at, min(step, mine - at), out)
+                    out = {"ratio_est": ratio_pi[i]}
+                    for at in range(0, mine, step):
+                        eng.run_calib(i, a.seed, first + at, min(step, mine - at), out, branch="perfect")
             rate_s = time.perf_counter() - t1
     if a.calibrate:
         # rho = ratio / reps over every rank's realisations (the sums are exchanged like the MSE sums; --rate
@@ -207,11 +218,16 @@ def main(argv=None):
             dev = "cuda" if os.environ.get("DSCE_DIST_BACKEND", "nccl") == "nccl" else None
             ratio_e = [allreduce_counts(r, dev) for r in ratio_e]
             ratio_p = [allreduce_counts(r, dev) for r in ratio_p]
+            ratio_pi = [allreduce_counts(r, dev) for r in ratio_pi]
         for i in range(len(names) if mine else 0):
             eng.set_llr_scale(i, ratio_e[i] / reps, ratio_p[i] / reps)
             out = {"loss_est": closs_e[i], "loss_perf0": closs_p[i]}
             for at in range(0, mine, step):
                 eng.run_soft(i, a.seed, first + at, min(step, mine - at), a.rate, out)
+            eng.set_llr_scale_perf(i, ratio_pi[i] / reps)
+            out = {"loss_est": closs_pi[i]}
+            for at in range(0, mine, step):
+                eng.run_soft(i, a.seed, first + at, min(step, mine - at), a.rate, out, branch="perfect")
         rate_s += time.perf_counter() - t1
     if eng is not None:
         eng.close()
@@ -253,9 +269,11 @@ def main(argv=None):
         if a.rate:
             loss_e = allreduce_counts(loss_e, dev)
             loss_p = allreduce_counts(loss_p, dev)
+            loss_pi = allreduce_counts(loss_pi, dev)
         if a.calibrate:
             closs_e = allreduce_counts(closs_e, dev)
             closs_p = allreduce_counts(closs_p, dev)
+            closs_pi = allreduce_counts(closs_pi, dev)
         # bits per realisation are a property of the schemes: every rank with work
         # has them (collective on every rank, so a rank with an empty shard too)
         have = np.array([0 if bits is None else 1], dtype=np.int64)
@@ -282,6 +300,7 @@ def main(argv=None):
             extra["bicm_rate"][s] = {
                 "mmse": {e: (m - loss_e[i, :, :, k] / (reps * nd[k])).tolist() for k, e in enumerate(EDGE)},
                 "perfect_onetap": {e: (m - loss_p[i, :, k] / (reps * nd[k])).tolist() for k, e in enumerate(EDGE)},
+                "perfect_ic": {e: (m - loss_pi[i, :, :, k] / (reps * nd[k])).tolist() for k, e in enumerate(EDGE)},
                 "method": a.rate}
             if a.calibrate:
                 # the same with pn_eff <- rho pn_eff; noise_ratio: the mean rho over the symbols of each edge class
@@ -292,10 +311,14 @@ def main(argv=None):
                                         for k, e in enumerate(EDGE)},
                     "perfect_onetap_calibrated": {e: (m - closs_p[i, :, k] / (reps * nd[k])).tolist()
                                                   for k, e in enumerate(EDGE)},
+                    "perfect_ic_calibrated": {e: (m - closs_pi[i, :, :, k] / (reps * nd[k])).tolist()
+                                              for k, e in enumerate(EDGE)},
                     "noise_ratio": {"mmse": {e: (ratio_e[i][:, :, sel[k]].mean(axis=-1) / reps).tolist()
                                              for k, e in enumerate(EDGE)},
                                     "perfect_onetap": {e: (ratio_p[i][:, sel[k]].mean(axis=-1) / reps).tolist()
-                                                       for k, e in enumerate(EDGE)}},
+                                                       for k, e in enumerate(EDGE)},
+                                    "perfect_ic": {e: (ratio_pi[i][:, :, sel[k]].mean(axis=-1) / reps).tolist()
+                                                   for k, e in enumerate(EDGE)}},
                     "calibration": {"reps": int(reps), "in_sample": True}})
     extra["realisations_per_s"] = reps / extra["seconds"]
     res = results.make(S, names, counts, bits, reps, a.seed, extra=extra)
@@ -319,6 +342,7 @@ def main(argv=None):
                               "bicm_rate_ic_mmse": r["mmse"]["all"][k][-1],
                               "bicm_rate_onetap_mmse": r["mmse"]["all"][k][0],
                               "bicm_rate_onetap_perfect": r["perfect_onetap"]["all"][k],
+                              "bicm_rate_ic_perfect": r["perfect_ic"]["all"][k][-1],
                               **({"bicm_rate_ic_mmse_calibrated": r["mmse_calibrated"]["all"][k][-1]}
                                  if a.calibrate else {})}
                           for s, r in extra["bicm_rate"].items()}))

@@ -95,6 +95,9 @@
  * DSCE_HAS_LLR_SCALE (still ABI 10) announces dsce_run_calib, dsce_set_llr_scale
  * and dsce_get_llr_scale: the demapper noise measured against the transmitted
  * symbols, and the soft calls' pn_eff scaled by it.
+ * DSCE_HAS_LLR_PERFECT (still ABI 10) announces the flag DSCE_LLR_PERFECT of
+ * dsce_export_llr, dsce_run_soft and dsce_run_calib (the perfect-CSI branch at
+ * every stage) with dsce_set_llr_scale_perf and dsce_get_llr_scale_perf.
  */
 #ifndef DSCE_H
 #define DSCE_H
@@ -513,9 +516,8 @@ typedef struct {          /* every pointer optional; C order; S = 1 + n_iter */
  * before channel, SNR points or scheme are set, and without dsce_build_mmse (an
  * interpolation scheme with n_iter == 0 needs none).  DSCE_EINVAL for a null
  * out, no field requested, an unknown flag or a bad device pointer.  On a
- * multi-device handle the export is member 0's.  The LLRs of the perfect-CSI
- * branch are not exported: form x_est / pn_eff from dsce_export's y and h and
- * call dsce_llr_awgn. */
+ * multi-device handle the export is member 0's.  With DSCE_LLR_PERFECT the three
+ * fields are those of the perfect-CSI branch (DSCE_HAS_LLR_PERFECT below). */
 int dsce_export_llr(dsce_ctx* ctx, int32_t scheme_id, uint64_t seed, uint64_t first_rep, uint64_t n_rep,
                     uint32_t flags, const dsce_export_llr_out* out);
 
@@ -541,8 +543,8 @@ int dsce_llr_info(dsce_ctx* ctx, int32_t scheme_id, int32_t* out2);
  *  dsce_export_llr exports.  [n_snr][1 + n_iter][2] doubles, C order.
  *  loss_perf0[snr][edge]: the same sum for the perfect-CSI one-tap receiver:
  *  x_est and pn_eff formed as for stage 0 with h (diag(D), the h of dsce_export)
- *  in place of h_est.  [n_snr][2] doubles.  The perfect-CSI IC stages have no
- *  such figure: the bulk mode does not stage y_perf.
+ *  in place of h_est.  [n_snr][2] doubles.  The perfect-CSI IC stages: call with
+ *  DSCE_LLR_PERFECT (DSCE_HAS_LLR_PERFECT below).
  *  Rate: I = m - loss / (n_rep ND_edge) bits per data symbol, ND_edge m from
  *  dsce_bits_per_rep.  With the exact LLRs this is the estimate of the BICM
  *  mutual information of the demapper output (the achievable rate of
@@ -566,8 +568,8 @@ typedef struct {          /* each optional */
  * MSE sums or dsce_path_info), with "k_llr_info" (its name under
  * dsce_enable_timing) after each SNR chunk: the LLRs are reduced on the device,
  * in a fixed order without atomics, so two identical calls return identical
- * bits; a few doubles reach the host once per call.  flags: 0 | DSCE_LLR_MAXLOG;
- * any other bit (DSCE_EXPORT_F32 and DSCE_EXPORT_DEVICE too) is DSCE_EINVAL, as
+ * bits; a few doubles reach the host once per call.  flags: 0 | DSCE_LLR_MAXLOG
+ * | DSCE_LLR_PERFECT; any other bit (DSCE_EXPORT_F32 and DSCE_EXPORT_DEVICE too) is DSCE_EINVAL, as
  * are a null out and no field requested.  DSCE_ESTATE as for dsce_export_llr.
  * On a multi-device handle the call is member 0's. */
 int dsce_run_soft(dsce_ctx* ctx, int32_t scheme_id, uint64_t seed, uint64_t first_rep, uint64_t n_rep,
@@ -610,8 +612,8 @@ typedef struct {            /* each optional */
  * name under dsce_enable_timing) after each SNR chunk: summed on the device in
  * a fixed order without atomics, so two identical calls return identical bits.
  * It always measures against the unscaled pn_eff: a call with tables installed
- * returns the bits of a call without.  flags must be 0: any bit is DSCE_EINVAL,
- * as are a null out and no field requested.  DSCE_ESTATE as for dsce_run_soft.
+ * returns the bits of a call without.  flags must be 0 or DSCE_LLR_PERFECT: any
+ * other bit is DSCE_EINVAL, as are a null out and no field requested.  DSCE_ESTATE as for dsce_run_soft.
  * On a multi-device handle the call is member 0's. */
 int dsce_run_calib(dsce_ctx* ctx, int32_t scheme_id, uint64_t seed, uint64_t first_rep, uint64_t n_rep,
                    uint32_t flags, const dsce_calib_out* out);
@@ -632,6 +634,57 @@ int dsce_set_llr_scale(dsce_ctx* ctx, int32_t scheme_id, const double* g_est, co
  * copied out, 1.0 everywhere for one that is not installed.  Every pointer
  * optional.  DSCE_ESTATE before dsce_set_snr. */
 int dsce_get_llr_scale(dsce_ctx* ctx, int32_t scheme_id, double* g_est, double* g_perf0, int32_t* set2);
+
+/* ---- the perfect-CSI branch of the soft calls (DSCE_HAS_LLR_PERFECT; additive,
+ *      ABI 10) -------------------------------------------------------------- */
+/* DSCE_LLR_PERFECT, in the flags word shared with DSCE_EXPORT_* and
+ * DSCE_LLR_MAXLOG (bit 3 stays an unknown flag), makes dsce_export_llr,
+ * dsce_run_soft and dsce_run_calib work on the perfect-CSI branch, with the same
+ * output structs and shapes.  Demapper input of stage s, data symbol j:
+ *    y_perf,0 = y;   y_perf,s = y - (D - diag h) u_(s-1) for s >= 1 (script:541-543),
+ *    u_(s-1) the re-precoded perfect-CSI decisions of stage s - 1 (the dec_perf of
+ *    dsce_export_stages); h = diag(D), the h of dsce_export, at every stage;
+ *    select schemes:   x_est_j  = y_perf,s[l] / h[l] / data_div
+ *                      pn_eff_j = Pn_l / (|h[l]|^2 data_div^2),  l = data_pos[j]
+ *    despread schemes: x_est_j  = sum_l conj(P[l, NP+j]) y_perf,s[l] / h[l] / data_div
+ *                      pn_eff_j = sum_l |P[l, NP+j]|^2 Pn_l / |h[l]|^2 / data_div^2
+ *  with real_detect handled as for the MMSE branch.  Without a table pn_eff does
+ *  not depend on the stage.  The arithmetic is the statement sequence of the MMSE
+ *  branch and of the one-tap pseudo-stage: a flagged stage 0 returns the bits of
+ *  loss_perf0 / ratio_perf0.
+ *  dsce_export_llr: x_est, pn_eff and llr are the perfect-CSI branch's.
+ *  dsce_run_soft:   loss_est[snr][stage][edge] receives the perfect-CSI sums; a
+ *                   non-null loss_perf0 is DSCE_EINVAL (it is stage 0 of the array).
+ *  dsce_run_calib:  ratio_est / ratio_perf0 by the same rule; always against the
+ *                   unscaled pn_eff.
+ *  A flagged call also stages y_perf of every stage, [stage][LK][unit], which
+ *  counts towards the export_stage_mb bound; an unflagged call allocates and
+ *  stores what it did.  Rows of the staging that a path does not form are not
+ *  read: the paths with the detection fused into the perfect-CSI pass (select
+ *  schemes with a row-local precoder: OFDM) form the data rows only, pilot rows
+ *  and stage 0 (read from y) stay NaN there; the other paths (FBMC auxiliary
+ *  and coded) form every row of the stages >= 1 and leave stage 0 NaN.  On the default OFDM and FBMC
+ *  paths every requested output entry is formed.  Batches, SNR chunks,
+ *  sub-batches, padding realisations, n_rep = 0, the absence of side effects, the
+ *  error codes and "member 0's on a multi-device handle" are those of the
+ *  unflagged calls, and without the flag every call returns the bits it returned
+ *  before.  Not built: both branches in one call. */
+#define DSCE_HAS_LLR_PERFECT 1
+#define DSCE_LLR_PERFECT (1u << 4)     /* shares the flags word of DSCE_EXPORT_* and DSCE_LLR_MAXLOG */
+
+/* The scale table of the flagged calls: g_perf [n_snr][1 + n_iter][ND] (C order;
+ * typically rho of a flagged dsce_run_calib); null removes it.  While installed,
+ * the flagged dsce_export_llr and dsce_run_soft form pn_eff <- g_perf[k][s][j]
+ * pn_eff, one multiplication after the unscaled value; x_est keeps its bits.
+ * g_est and g_perf0 do not touch the flagged calls and g_perf does not touch the
+ * unflagged ones.  Every entry must be finite and > 0, else DSCE_EINVAL and the
+ * installed table stays.  Needs dsce_set_snr (DSCE_ESTATE) and the scheme, not
+ * dsce_build_mmse; dsce_set_snr drops the table.  A configuration call: on a
+ * multi-device handle it reaches every member. */
+int dsce_set_llr_scale_perf(dsce_ctx* ctx, int32_t scheme_id, const double* g_perf);
+/* set1[0] = 1 where g_perf is installed; the table is copied out, 1.0 everywhere
+ * when it is not.  Every pointer optional.  DSCE_ESTATE before dsce_set_snr. */
+int dsce_get_llr_scale_perf(dsce_ctx* ctx, int32_t scheme_id, double* g_perf, int32_t* set1);
 
 /* ---- engine state ------------------------------------------------------- */
 int dsce_scheme_dims(dsce_ctx* ctx, int32_t scheme_id, dsce_dims* dims);
