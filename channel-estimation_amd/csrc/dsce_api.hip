@@ -764,13 +764,30 @@ void pack_scheme(dsce_ctx* c, Scheme& s) {
     }
     // slicer grid of the constellation
     std::vector<double> lvI, lvQ;
-    for (auto& z : s.symbols) { lvI.push_back(z.x); lvQ.push_back(z.y); }
+    for (auto& z : s.symbols) {
+        if (!std::isfinite(z.x) || !std::isfinite(z.y)) throw ApiError(DSCE_EINVAL, "constellation symbol is not finite");
+        lvI.push_back(z.x);
+        lvQ.push_back(z.y);
+    }
     std::sort(lvI.begin(), lvI.end());
     lvI.erase(std::unique(lvI.begin(), lvI.end()), lvI.end());
     std::sort(lvQ.begin(), lvQ.end());
     lvQ.erase(std::unique(lvQ.begin(), lvQ.end()), lvQ.end());
     if ((int)(lvI.size() * lvQ.size()) != s.d.mod_order)
         throw ApiError(DSCE_EINVAL, "constellation is not a full rectangular grid");
+    // every slicer takes the cell index from (x - lv[0]) / (lv[1] - lv[0]): the levels of an axis must be
+    // equally spaced (the reference's tables deviate by a few ulp; 1e-9 of the span is far inside a cell)
+    auto check_spacing = [](const std::vector<double>& lv, const char* axis) {
+        const int n = (int)lv.size();
+        if (n < 3) return;
+        const double span = lv[n - 1] - lv[0];
+        for (int i = 0; i < n; ++i)
+            if (!(std::fabs(lv[i] - (lv[0] + i * span / (n - 1))) <= 1e-9 * span))
+                throw ApiError(DSCE_EINVAL, std::string("constellation levels of the ") + axis +
+                                                " axis are not equally spaced (level " + std::to_string(i) + ")");
+    };
+    check_spacing(lvI, "I");
+    check_spacing(lvQ, "Q");
     std::vector<int> grid(lvI.size() * lvQ.size(), -1);
     for (int m = 0; m < s.d.mod_order; ++m) {
         const int iI = (int)(std::lower_bound(lvI.begin(), lvI.end(), s.symbols[m].x) - lvI.begin());

@@ -161,7 +161,14 @@ typedef struct {
     const int32_t* pilot_pos;   /* n_pilots positions in 0..LK-1               */
     const int32_t* data_pos;    /* n_data positions (select mode)              */
     const uint8_t* considered;  /* n_data no-edge flags (script:151-172)       */
-    const double* symbols;      /* M complex, SymbolMapping sorted by bit label */
+    const double* symbols;      /* M complex, SymbolMapping sorted by bit label. */
+                                /* Finite points that fill a rectangular nI x nQ */
+                                /* grid (nI nQ = M, any labelling, any offset);  */
+                                /* an axis with three or more levels must be     */
+                                /* equally spaced: |lv[i] - (lv[0] + i (lv[n-1] -*/
+                                /* lv[0]) / (n-1))| <= 1e-9 (lv[n-1] - lv[0]),   */
+                                /* the slicers index by (x - lv[0]) / step.      */
+                                /* Otherwise DSCE_EINVAL, naming the axis.       */
 } dsce_scheme_desc;
 
 /* On-GPU producer of the transmit / receive matrices,

@@ -52,13 +52,14 @@ def _export(eng, sid, seed, first, n, fields=ALL, dtype=np.complex128, flags=Non
 _ORACLE = {}
 
 
-def _oracle_units(S, name, first, n):
+def _oracle_units(S, name, first, n, seed=SEED):
     """refsim.simulate's per-unit trace of realisations [first, first + n),
-    as units[i][k] (realisation i, SNR index k); computed once per range."""
-    key = (S.name, tuple(S.snr_db), S.n_iter, name, first, n)
+    as units[i][k] (realisation i, SNR index k); computed once per range (and
+    per seed and constellation table: tests replace a setup's table)."""
+    key = (S.name, tuple(S.snr_db), S.n_iter, name, first, n, seed, np.asarray(S.schemes[name]["symbols"]).tobytes())
     if key not in _ORACLE:
         tr = {}
-        harness.simulate(S, SEED, first, n, [name], trace=tr)
+        harness.simulate(S, seed, first, n, [name], trace=tr)
         ns = len(S.pn_time)
         _ORACLE[key] = [[tr["units"][i * ns + k] for k in range(ns)] for i in range(n)]
     return _ORACLE[key]

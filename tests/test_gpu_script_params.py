@@ -265,8 +265,9 @@ def _oracle_counts(S, name):
     return res
 
 
-def _check_counts(eng, res, what=""):
-    cg = eng.run(SEED, 0, 64)
+def _check_counts(eng, res, what="", n=64):
+    """The run's counters of realisations 0..n-1 against the oracle's res of the same range."""
+    cg = eng.run(SEED, 0, n)
     assert cg.shape == res["err"].shape
     assert np.abs(cg - res["err"]).sum() <= 8 * res["borderline"].sum(), (what, eng.path_info(0), cg - res["err"])
     return eng.path_info(0)
@@ -331,10 +332,11 @@ def test_fbmc_constellation_orders(qam):
 
 
 def test_1024_qam_is_rejected_cleanly():
-    """The engine's symbol indices, LDS constellation and byte-grid slicer hold
-    at most 256 symbols and 16 levels per axis.  1024-QAM is turned away at
-    dsce_add_scheme with DSCE_EINVAL before anything is built, so no kernel
-    ever sees 32 levels per axis; the context stays usable: the scheme it
+    """The engine's symbol indices and LDS constellation hold at most 256
+    symbols.  1024-QAM is turned away at dsce_add_scheme with DSCE_EINVAL before
+    anything is built, so no kernel ever sees more than 256 symbols (32 levels on
+    an axis do reach the engine, with 32-PAM or 32 x 8: the fallback slicer of
+    tests/test_gpu_constellations.py); the context stays usable: the scheme it
     already holds counts exactly as before and on the same kernels."""
     from dsce.engine import DsceError
     S = harness.setup("default", schemes=("ofdm",), snr_db=SNR)
