@@ -154,6 +154,8 @@ struct McBuffers {
     const TraceK* tr; // device trace of one unit (null: not tracing this scheme / chunk)
     int tr_bulk;      // tr is in bulk mode (TraceK::U > 0): the launchers pick the bulk instances
     int tr_yperf;     // ... and TraceK::yperf is non-null (DSCE_LLR_PERFECT): the instances that stage y_perf
+    bool bulk() const { return tr && tr_bulk; }           // a kernel with a bulk twin launches the twin
+    bool bulk_y() const { return bulk() && tr_yperf; }    // ... the twin that stages y_perf
 };
 
 struct MmseK {

@@ -14,6 +14,7 @@
 // wanted (matvec inner loops).
 #include "dsce_kernels.h"
 #include "bm_tables.h"
+#include "dsce_dispatch.h"
 
 #include <math.h>
 #include <algorithm>
@@ -916,34 +917,30 @@ int launch_jakes(hipStream_t s, const Opts& op, const ChannelK& ch, uint64_t see
             (jc->ngrp == 1 || jc->ngrp == 2 || jc->ngrp == 4) && (size_t)32 * ch.paths * sizeof(double) <= 64 * 1024) {
             const dim3 grid(R / 8);
             const size_t lds = (size_t)32 * ch.paths * sizeof(double);
-#define LAUNCH_JGRP2(MT_, NG_)                                                                                 \
-    if (jc->mt == MT_ && jc->ngrp == NG_) {                                                                   \
-        ji = JakesInfo{JAKES_K_WIN_GRP, 1, NG_, 16 / NG_, MT_, jc->n};                                        \
-        hipLaunchKernelGGL((k_jakes_grp2<MT_, 16 / NG_>), grid, dim3(256), lds, s, ch, seed, rep0, R, ir,     \
-                           jc->n0, jc->grp, jc->ngrp);                                                        \
-        return JAKES_KIND_GRP;                                                                                \
-    }
-            LAUNCH_JGRP2(16, 1) LAUNCH_JGRP2(16, 2) LAUNCH_JGRP2(16, 4)
-            LAUNCH_JGRP2(24, 1) LAUNCH_JGRP2(24, 2) LAUNCH_JGRP2(24, 4)
-            LAUNCH_JGRP2(28, 1) LAUNCH_JGRP2(28, 2) LAUNCH_JGRP2(28, 4)
-#undef LAUNCH_JGRP2
+            bool hit = false;
+            for_value<16, 24, 28>(jc->mt, [&](auto MT) {
+                hit = for_value<1, 2, 4>(jc->ngrp, [&](auto NG) {
+                    ji = JakesInfo{JAKES_K_WIN_GRP, 1, NG, 16 / NG, MT, jc->n};
+                    hipLaunchKernelGGL((k_jakes_grp2<MT, 16 / NG>), grid, dim3(256), lds, s, ch, seed, rep0, R, ir,
+                                       jc->n0, jc->grp, jc->ngrp);
+                });
+            });
+            if (hit) return JAKES_KIND_GRP;
         }
         if (op.jakes_mom == 2 && jc->ngrp > 0) {
             constexpr int RPW = 2;
             const int gpb = WAVE / RPW / jc->lg;
             dim3 grid((jc->ngrp + gpb - 1) / gpb, R / (4 * RPW), ch.ntap);
             const size_t lds = (size_t)4 * RPW * 3 * ch.paths * sizeof(double);
-#define LAUNCH_JGRP(MT_, LG_)                                                                                 \
-    if (jc->mt == MT_ && jc->lg == LG_) {                                                                    \
-        ji = JakesInfo{JAKES_K_WIN_GRP, 0, jc->ngrp, LG_, MT_, jc->n};                                       \
-        hipLaunchKernelGGL((k_jakes_grp<MT_, LG_>), grid, dim3(256), lds, s, ch, seed, rep0, R, ir, jc->n0,  \
-                           jc->grp, jc->ngrp);                                                               \
-        return JAKES_KIND_GRP;                                                                               \
-    }
-            LAUNCH_JGRP(16, 4) LAUNCH_JGRP(16, 8) LAUNCH_JGRP(16, 16)
-            LAUNCH_JGRP(24, 4) LAUNCH_JGRP(24, 8) LAUNCH_JGRP(24, 16)
-            LAUNCH_JGRP(28, 4) LAUNCH_JGRP(28, 8) LAUNCH_JGRP(28, 16)
-#undef LAUNCH_JGRP
+            bool hit = false;
+            for_value<16, 24, 28>(jc->mt, [&](auto MT) {
+                hit = for_value<4, 8, 16>(jc->lg, [&](auto LG) {
+                    ji = JakesInfo{JAKES_K_WIN_GRP, 0, jc->ngrp, LG, MT, jc->n};
+                    hipLaunchKernelGGL((k_jakes_grp<MT, LG>), grid, dim3(256), lds, s, ch, seed, rep0, R, ir, jc->n0,
+                                       jc->grp, jc->ngrp);
+                });
+            });
+            if (hit) return JAKES_KIND_GRP;
         }
         if (op.jakes_mom && JakesChunks::LEN == 24 && TWO_PI * fabs(ch.fD) * ch.dt * 11.5 <= 0.3) {
             constexpr int RPW = 2, CPW = WAVE / RPW / 2;
@@ -964,41 +961,12 @@ int launch_jakes(hipStream_t s, const Opts& op, const ChannelK& ch, uint64_t see
     const int jch2 = (ch.N + WAVE / 2 - 1) / (WAVE / 2);
     if (jch2 >= 9 && jch2 <= 20 && R % 8 == 0 && (size_t)8 * 4 * ch.paths * sizeof(double) <= 64 * 1024 &&
         op.jakes_rpw == 2) {
-        switch (jch2) {
-            case 9: launch_jakes_t<9, 2>(s, ch, seed, rep0, R, ir); return JAKES_KIND_OTHER;
-            case 10: launch_jakes_t<10, 2>(s, ch, seed, rep0, R, ir); return JAKES_KIND_OTHER;
-            case 11: launch_jakes_t<11, 2>(s, ch, seed, rep0, R, ir); return JAKES_KIND_OTHER;
-            case 12: launch_jakes_t<12, 2>(s, ch, seed, rep0, R, ir); return JAKES_KIND_OTHER;
-            case 13: launch_jakes_t<13, 2>(s, ch, seed, rep0, R, ir); return JAKES_KIND_OTHER;
-            case 14: launch_jakes_t<14, 2>(s, ch, seed, rep0, R, ir); return JAKES_KIND_OTHER;
-            case 15: launch_jakes_t<15, 2>(s, ch, seed, rep0, R, ir); return JAKES_KIND_OTHER;
-            case 16: launch_jakes_t<16, 2>(s, ch, seed, rep0, R, ir); return JAKES_KIND_OTHER;
-            case 17: launch_jakes_t<17, 2>(s, ch, seed, rep0, R, ir); return JAKES_KIND_OTHER;
-            case 18: launch_jakes_t<18, 2>(s, ch, seed, rep0, R, ir); return JAKES_KIND_OTHER;
-            case 19: launch_jakes_t<19, 2>(s, ch, seed, rep0, R, ir); return JAKES_KIND_OTHER;
-            default: launch_jakes_t<20, 2>(s, ch, seed, rep0, R, ir); return JAKES_KIND_OTHER;
-        }
+        for_range<9, 20>(jch2, [&](auto JCH) { launch_jakes_t<JCH, 2>(s, ch, seed, rep0, R, ir); });
+        return JAKES_KIND_OTHER;
     }
     int jch = (ch.N + WAVE - 1) / WAVE;           // samples per lane: one wave covers N when N <= 1024
     if (jch > JCH_MAX) jch = JCH_MAX;
-    switch (jch) {
-        case 1: launch_jakes_t<1>(s, ch, seed, rep0, R, ir); break;
-        case 2: launch_jakes_t<2>(s, ch, seed, rep0, R, ir); break;
-        case 3: launch_jakes_t<3>(s, ch, seed, rep0, R, ir); break;
-        case 4: launch_jakes_t<4>(s, ch, seed, rep0, R, ir); break;
-        case 5: launch_jakes_t<5>(s, ch, seed, rep0, R, ir); break;
-        case 6: launch_jakes_t<6>(s, ch, seed, rep0, R, ir); break;
-        case 7: launch_jakes_t<7>(s, ch, seed, rep0, R, ir); break;
-        case 8: launch_jakes_t<8>(s, ch, seed, rep0, R, ir); break;
-        case 9: launch_jakes_t<9>(s, ch, seed, rep0, R, ir); break;
-        case 10: launch_jakes_t<10>(s, ch, seed, rep0, R, ir); break;
-        case 11: launch_jakes_t<11>(s, ch, seed, rep0, R, ir); break;
-        case 12: launch_jakes_t<12>(s, ch, seed, rep0, R, ir); break;
-        case 13: launch_jakes_t<13>(s, ch, seed, rep0, R, ir); break;
-        case 14: launch_jakes_t<14>(s, ch, seed, rep0, R, ir); break;
-        case 15: launch_jakes_t<15>(s, ch, seed, rep0, R, ir); break;
-        default: launch_jakes_t<16>(s, ch, seed, rep0, R, ir); break;
-    }
+    for_range<1, JCH_MAX>(jch, [&](auto JCH) { launch_jakes_t<JCH>(s, ch, seed, rep0, R, ir); });
     return JAKES_KIND_OTHER;
 }
 
@@ -1562,25 +1530,6 @@ struct LoadNoisy {
     __device__ __forceinline__ double2 combine(const Regs& r) const { return r; }
 };
 
-static unsigned launch_txrx(hipStream_t s, const Opts& op, const SchemeK& sk, const ChannelK& ch, const double* pn,
-                            uint64_t seed, uint64_t rep0, McBuffers& b);
-
-unsigned launch_rx_front(hipStream_t s, const Opts& op, const SchemeK& sk, const ChannelK& ch, const double* pn,
-                         uint64_t seed, uint64_t rep0, McBuffers& b) {
-    if (txrx_fft_ok(op, sk, ch, b)) return launch_txrx(s, op, sk, ch, pn, seed, rep0, b);
-    if (sk.qh_disjoint && op.noise_fuse) {
-        launch_band(s, sk.QH, b.U, nullptr, LoadNoisy{b.r0, pn, seed, rep0, b.R, b.snr0, sk.noise_slot, op.snr_base},
-                    StoreSoA{b.y, b.U});
-        return PATH_NOISE_FUSED;
-    }
-    hipLaunchKernelGGL(k_noise, dim3(b.U / WAVE, (sk.N + 63) / 64), dim3(WAVE), 0, s, sk.N, b.R, b.U, b.snr0, sk.noise_slot,
-                       op.snr_base, pn, seed, rep0,
-                       b.r0, b.t);
-    // y = Q' r (script:406-409)
-    launch_band(s, sk.QH, b.U, nullptr, LoadSoA{b.t, b.U}, StoreSoA{b.y, b.U});
-    return 0;
-}
-
 typedef double d4 __attribute__((ext_vector_type(4)));
 
 #define MFMA64(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
@@ -1605,7 +1554,7 @@ __device__ __forceinline__ unsigned buf_ldu16(__amdgpu_buffer_rsrc_t r, unsigned
 // array: a buffer view from the block's first row, the lane's byte offset
 // (r ld + col) esz, and row a at the wave-uniform offset 4 a ld esz (SGPR): no
 // 64-bit address arithmetic per load (r05; the chain kernels' prologues spent
-// ~3 VALU per row and array on it).  Callers: 24 ld esz < 2^32 (pic_fft_ok).
+// ~3 VALU per row and array on it).  Callers: 24 ld esz < 2^32 (perfect_chain_ok).
 struct RowView {
     __amdgpu_buffer_rsrc_t rs;
     unsigned voff, step;
@@ -3056,8 +3005,6 @@ k_txrx_fft(SchemeK sk, TxrxArgs ta, int xcd) {
     }
 }
 
-bool txrx_fft_ok(const Opts& op, const SchemeK& sk, const ChannelK& ch, const McBuffers& b);
-
 template <int NT, class Out>
 static void launch_pass2(hipStream_t s, const SchemeK& sk, const ChannelK& ch, McBuffers& b, const BandOrder& ord,
                          const Out& o, size_t lds) {
@@ -3075,15 +3022,9 @@ static void launch_pass2(hipStream_t s, const SchemeK& sk, const ChannelK& ch, M
 template <class Out>
 static void launch_pass2_nt(hipStream_t s, const SchemeK& sk, const ChannelK& ch, McBuffers& b, const BandOrder& ord,
                             const Out& o, size_t lds = 0) {
-    switch (ch.ntap) {
-        case 1: launch_pass2<1>(s, sk, ch, b, ord, o, lds); break;
-        case 2: launch_pass2<2>(s, sk, ch, b, ord, o, lds); break;
-        case 3: launch_pass2<3>(s, sk, ch, b, ord, o, lds); break;
-        case 4: launch_pass2<4>(s, sk, ch, b, ord, o, lds); break;
-        case 5: launch_pass2<5>(s, sk, ch, b, ord, o, lds); break;
-        case 6: launch_pass2<6>(s, sk, ch, b, ord, o, lds); break;
-        default: launch_pass2<0>(s, sk, ch, b, ord, o, lds); break;
-    }
+    // 1-6 taps unrolled, any other count by the run-time loop (NT = 0)
+    if (!for_range<1, 6>(ch.ntap, [&](auto NT) { launch_pass2<NT>(s, sk, ch, b, ord, o, lds); }))
+        launch_pass2<0>(s, sk, ch, b, ord, o, lds);
 }
 
 // Opts::pic_chain: 0 = per-iteration passes (G u pass + Q^H H pass), 3 (default)
@@ -3097,6 +3038,19 @@ static int pic_fft_shift(const ChannelK& ch) {
         sh |= ch.tap_delay[q] << q;
     }
     return (ch.ntap == 1 && sh == 0) || (ch.ntap == 2 && (sh == 1 || sh == 2)) ? sh : -1;
+}
+// f(NT, SH) with the tap shape of the channel as constants: the (NT, SH)
+// instances of k_txrx_fft, k_pic_fft, k_mic_pilot and k_mic_data.  False (and
+// no call) when there is none.
+template <class F>
+static bool for_tap_shape(const ChannelK& ch, F&& f) {
+    using std::integral_constant;
+    switch (pic_fft_shift(ch)) {
+        case 0: f(integral_constant<int, 1>{}, integral_constant<int, 0>{}); return true;
+        case 1: f(integral_constant<int, 2>{}, integral_constant<int, 1>{}); return true;
+        case 2: f(integral_constant<int, 2>{}, integral_constant<int, 2>{}); return true;
+        default: return false;
+    }
 }
 
 // k_txrx_fft applies: FFT-form OFDM blocks, at most two taps with delays <= 1,
@@ -3124,13 +3078,30 @@ static unsigned launch_txrx(hipStream_t s, const Opts& op, const SchemeK& sk, co
     ta.slot = sk.noise_slot;
     ta.base = op.snr_base;
     const dim3 grid((b.R / WAVE) * sk.QH.nblk), blk(256);
-    if (ch.ntap == 1) hipLaunchKernelGGL((k_txrx_fft<1, 0>), grid, blk, 0, s, sk, ta, op.xcd);
-    else if (pic_fft_shift(ch) == 1) hipLaunchKernelGGL((k_txrx_fft<2, 1>), grid, blk, 0, s, sk, ta, op.xcd);
-    else hipLaunchKernelGGL((k_txrx_fft<2, 2>), grid, blk, 0, s, sk, ta, op.xcd);
+    if (!for_tap_shape(ch, [&](auto NT, auto SH) {
+            hipLaunchKernelGGL((k_txrx_fft<NT, SH>), grid, blk, 0, s, sk, ta, op.xcd);
+        }))
+        throw std::logic_error("launch_txrx: no k_txrx_fft instance for the channel's taps (txrx_fft_ok is false)");
     return PATH_NOISE_FUSED | PATH_TXRX_FFT;
 }
 
-static bool pic_fft_ok(const Opts& op, const SchemeK& sk, const ChannelK& ch, const McBuffers& b, int niter) {
+unsigned launch_rx_front(hipStream_t s, const Opts& op, const SchemeK& sk, const ChannelK& ch, const double* pn,
+                         uint64_t seed, uint64_t rep0, McBuffers& b) {
+    if (txrx_fft_ok(op, sk, ch, b)) return launch_txrx(s, op, sk, ch, pn, seed, rep0, b);
+    if (sk.qh_disjoint && op.noise_fuse) {
+        launch_band(s, sk.QH, b.U, nullptr, LoadNoisy{b.r0, pn, seed, rep0, b.R, b.snr0, sk.noise_slot, op.snr_base},
+                    StoreSoA{b.y, b.U});
+        return PATH_NOISE_FUSED;
+    }
+    hipLaunchKernelGGL(k_noise, dim3(b.U / WAVE, (sk.N + 63) / 64), dim3(WAVE), 0, s, sk.N, b.R, b.U, b.snr0, sk.noise_slot,
+                       op.snr_base, pn, seed, rep0,
+                       b.r0, b.t);
+    // y = Q' r (script:406-409)
+    launch_band(s, sk.QH, b.U, nullptr, LoadSoA{b.t, b.U}, StoreSoA{b.y, b.U});
+    return 0;
+}
+
+bool perfect_chain_ok(const Opts& op, const SchemeK& sk, const ChannelK& ch, const McBuffers& b, int niter) {
     const bool fits = (long long)24 * b.U * 16 < (1ll << 32) && (long long)ch.ntap * ch.N * b.R * 16 < (1ll << 32) &&
                       (long long)sk.LK * b.U < (1ll << 62);
     // slice6's byte grid: nI, nQ <= 16 levels, M <= 256 symbols
@@ -3138,14 +3109,10 @@ static bool pic_fft_ok(const Opts& op, const SchemeK& sk, const ChannelK& ch, co
            sk.M <= 256 && sk.nI <= 16 && sk.nQ <= 16;
 }
 
-bool perfect_chain_ok(const Opts& op, const SchemeK& sk, const ChannelK& ch, const McBuffers& b, int niter) {
-    return pic_fft_ok(op, sk, ch, b, niter);
-}
-
-// Detection operands of the chain kernels (k_pic_fft / k_mic_pilot /
-// k_mic_data): tables, slicer folded for nearest_lin, counters of branch `csi`
-// (0 MMSE, 1 perfect CSI; the stage is added per iteration).
-static StorePerfectDetect chain_detect(const SchemeK& sk, const McBuffers& b, const PerfectDetectArgs* pd, int csi) {
+// Detection operands every user of StorePerfectDetect fills alike: buffers,
+// tables, slicer steps and the counters of branch `csi` (0 MMSE, 1 perfect CSI)
+// at stage 0; the caller adds its stage, or the kernel does per iteration.
+static StorePerfectDetect detect_operands(const SchemeK& sk, const McBuffers& b, const PerfectDetectArgs* pd, int csi) {
     StorePerfectDetect o{};
     o.tr = b.tr;
     o.y = b.y;
@@ -3174,6 +3141,14 @@ static StorePerfectDetect chain_detect(const SchemeK& sk, const McBuffers& b, co
     o.idd = 1.0 / sk.data_div;
     o.sI = pd->sI;
     o.sQ = pd->sQ;
+    return o;
+}
+
+// ... of the chain kernels (k_pic_fft / k_mic_pilot / k_mic_data): with the
+// transmitted symbols, the precoder's pilot values and the slicer folded for
+// nearest_lin
+static StorePerfectDetect chain_detect(const SchemeK& sk, const McBuffers& b, const PerfectDetectArgs* pd, int csi) {
+    StorePerfectDetect o = detect_operands(sk, b, pd, csi);
     o.xp = b.xp;
     o.xs = b.xs;
     o.sidr = b.sidr;
@@ -3202,7 +3177,7 @@ bool mmse_stages_ok(const Opts& op, const SchemeK& sk, const MmseK& mm, const Ch
     return op.mmse_ic == 1 && mm.Bv && mm.Bs && sk.pf_ok && sk.NP == 16 && pic_fft_shift(ch) >= 0 &&
            (b.U % 64) == 0 && (b.R % 64) == 0 && fits && mm.npb >= 1 && mm.npb <= 4 && mm.ndb >= 1 && b.hpa &&
            niter >= 1 && niter <= PM_MAXIT && b.hpa_stages >= niter + 1 && op.pic_chain == 3 &&
-           pic_fft_ok(op, sk, ch, b, niter) && (long long)(niter + 1) * sk.NP * b.U < (1ll << 40);
+           perfect_chain_ok(op, sk, ch, b, niter) && (long long)(niter + 1) * sk.NP * b.U < (1ll << 40);
 }
 
 static Mic2Args mic2_args(const SchemeK& sk, const MmseK& mm, const ChannelK& ch, const McBuffers& b,
@@ -3233,41 +3208,26 @@ unsigned launch_mmse_stages(hipStream_t s, const SchemeK& sk, const MmseK& mm, c
     Mic2Args ma = mic2_args(sk, mm, ch, b, pd, niter);
     // the low-rank operator: built (build_mic_lr), MIC_NB pilot symbols, Z buffer
     const bool use_lr = lr && mm.Bz && mm.Tw && mm.Ts && b.za && mm.npb == MIC_NB;
-    const int sh = pic_fft_shift(ch);
-    // pilot symbols: one wave each, 16 units per block
-    ma.blks = mm.pblk;
-    ma.nb = mm.npb;
-    if (part & 1) {
-        const dim3 grid(b.U / 16), blk(64 * mm.npb);
-#define LAUNCH_MP(NTV, SHV)                                                                                  \
-    do {                                                                                                     \
-        if (use_lr && b.tr) hipLaunchKernelGGL((k_mic_pilot<NTV, SHV, 16, true, true>), grid, blk, 0, s, sk, ma, o); \
-        else if (use_lr) hipLaunchKernelGGL((k_mic_pilot<NTV, SHV, 16, false, true>), grid, blk, 0, s, sk, ma, o); \
-        else if (b.tr) hipLaunchKernelGGL((k_mic_pilot<NTV, SHV, 16, true>), grid, blk, 0, s, sk, ma, o);   \
-        else hipLaunchKernelGGL((k_mic_pilot<NTV, SHV, 16, false>), grid, blk, 0, s, sk, ma, o);            \
-    } while (0)
-        if (ch.ntap == 1) LAUNCH_MP(1, 0);
-        else if (sh == 1) LAUNCH_MP(2, 1);
-        else LAUNCH_MP(2, 2);
-#undef LAUNCH_MP
-    }
-    ma.blks = mm.dblk;
-    ma.nb = mm.ndb;
-    if (part & 2) {
-        const BandOrder om{b.U / WAVE, b.U / b.R, b.R / WAVE, xcd};
-        const dim3 grid((b.U / WAVE) * mm.ndb), blk(256);
-#define LAUNCH_MD(NTV, SHV)                                                                                  \
-    do {                                                                                                     \
-        if (use_lr && b.tr) hipLaunchKernelGGL((k_mic_data<NTV, SHV, 16, true, true>), grid, blk, 0, s, sk, om, ma, o); \
-        else if (use_lr) hipLaunchKernelGGL((k_mic_data<NTV, SHV, 16, false, true>), grid, blk, 0, s, sk, om, ma, o); \
-        else if (b.tr) hipLaunchKernelGGL((k_mic_data<NTV, SHV, 16, true>), grid, blk, 0, s, sk, om, ma, o); \
-        else hipLaunchKernelGGL((k_mic_data<NTV, SHV, 16, false>), grid, blk, 0, s, sk, om, ma, o);         \
-    } while (0)
-        if (ch.ntap == 1) LAUNCH_MD(1, 0);
-        else if (sh == 1) LAUNCH_MD(2, 1);
-        else LAUNCH_MD(2, 2);
-#undef LAUNCH_MD
-    }
+    const bool hit = for_tap_shape(ch, [&](auto NT, auto SH) {
+        for_bool(b.tr != nullptr, [&](auto TR) {
+            for_bool(use_lr, [&](auto LR) {
+                // pilot symbols: one wave each, 16 units per block
+                ma.blks = mm.pblk;
+                ma.nb = mm.npb;
+                if (part & 1)
+                    hipLaunchKernelGGL((k_mic_pilot<NT, SH, 16, TR, LR>), dim3(b.U / 16), dim3(64 * mm.npb), 0, s, sk,
+                                       ma, o);
+                ma.blks = mm.dblk;
+                ma.nb = mm.ndb;
+                if (part & 2) {
+                    const BandOrder om{b.U / WAVE, b.U / b.R, b.R / WAVE, xcd};
+                    hipLaunchKernelGGL((k_mic_data<NT, SH, 16, TR, LR>), dim3((b.U / WAVE) * mm.ndb), dim3(256), 0, s,
+                                       sk, om, ma, o);
+                }
+            });
+        });
+    });
+    if (!hit) throw std::logic_error("launch_mmse_stages: no instance for the channel's taps (mmse_stages_ok is false)");
     return PATH_MIC_FFT | PATH_MIC_STAGES | (use_lr ? PATH_MIC_LR : 0u);
 }
 
@@ -3287,7 +3247,7 @@ static bool snr_loop_fills(const Opts& op, long long blocks) {
 
 unsigned launch_perfect_chain(hipStream_t s, const Opts& op, const SchemeK& sk, const ChannelK& ch, McBuffers& b,
                               const PerfectDetectArgs* pd, int niter, bool stage0) {
-    if (!pic_fft_ok(op, sk, ch, b, niter))
+    if (!perfect_chain_ok(op, sk, ch, b, niter))
         throw std::logic_error("launch_perfect_chain: no chain kernel for this scheme (perfect_chain_ok is false)");
     StorePerfectDetect o = chain_detect(sk, b, pd, 1);
     const BandOrder om{b.U / WAVE, b.U / b.R, b.R / WAVE, op.xcd};
@@ -3301,25 +3261,16 @@ unsigned launch_perfect_chain(hipStream_t s, const Opts& op, const SchemeK& sk, 
     // k_mic_data); otherwise stage 0 came from the stage kernel (u in HBM)
     if (!(o.scI != 0.0))
         throw std::logic_error("launch_perfect_chain: the chain's slicer scale is zero");
-#define LAUNCH_PF(NTV, SHV, S0V, LPV)                                                                               \
-    do {                                                                                                             \
-        if (b.tr)                                                                                                    \
-            hipLaunchKernelGGL((k_pic_fft<NTV, SHV, true, S0V, LPV>), grid, blk, 0, s, sk, om, b.ir, ch.N, o, niter);  \
-        else                                                                                                         \
-            hipLaunchKernelGGL((k_pic_fft<NTV, SHV, false, S0V, LPV>), grid, blk, 0, s, sk, om, b.ir, ch.N, o, niter); \
-    } while (0)
-#define LAUNCH_PF2(NTV, SHV)                               \
-    do {                                                   \
-        if (loop) LAUNCH_PF(NTV, SHV, true, true);         \
-        else if (stage0) LAUNCH_PF(NTV, SHV, true, false); \
-        else LAUNCH_PF(NTV, SHV, false, false);            \
-    } while (0)
-    const int sh = pic_fft_shift(ch);
-    if (ch.ntap == 1) LAUNCH_PF2(1, 0);
-    else if (sh == 1) LAUNCH_PF2(2, 1);
-    else LAUNCH_PF2(2, 2);
-#undef LAUNCH_PF2
-#undef LAUNCH_PF
+    // the (S0, LOOP) instances: 0 = (false, false), 1 = (true, false), 2 = (true, true)
+    const int form = loop ? 2 : stage0 ? 1 : 0;
+    for_tap_shape(ch, [&](auto NT, auto SH) {      // (a shape exists: perfect_chain_ok)
+        for_value<0, 1, 2>(form, [&](auto FORM) {
+            for_bool(b.tr != nullptr, [&](auto TR) {
+                hipLaunchKernelGGL((k_pic_fft<NT, SH, TR, (FORM >= 1), (FORM == 2)>), grid, blk, 0, s, sk, om, b.ir,
+                                   ch.N, o, niter);
+            });
+        });
+    });
     return PATH_PIC_FFT | (loop ? PATH_SNR_LOOP : 0u);
 }
 
@@ -3564,23 +3515,21 @@ static PolyArgs poly_args(const Opts& op, const SchemeK& sk, const ChannelK& ch,
 static void launch_poly_front(hipStream_t s, const SchemeK& sk, const ChannelK& ch, const PolyArgs& pa) {
     const int ng = pa.U / WAVE;
     const dim3 gs(ng * pa.K), gc(ng * 2 * sk.poly_F), blk(WAVE);
-#define POLY_CHAN(FV)                                                                              \
-    do {                                                                                           \
-        hipLaunchKernelGGL((k_poly_syn<FV>), gs, blk, 0, s, pa);                                   \
-        if (ch.ntap == 1) hipLaunchKernelGGL((k_poly_chan<FV, 1>), gc, blk, 0, s, pa);            \
-        else if (ch.ntap == 2) hipLaunchKernelGGL((k_poly_chan<FV, 2>), gc, blk, 0, s, pa);       \
-        else hipLaunchKernelGGL((k_poly_chan<FV, 3>), gc, blk, 0, s, pa);                         \
-    } while (0)
-    if (sk.poly_F == 24) POLY_CHAN(24);
-    else POLY_CHAN(48);
-#undef POLY_CHAN
+    // F is 24 or 48 and there are 1-3 taps (poly_launch_ok); the ladders' defaults are kept
+    for_value<24, 48>(sk.poly_F == 24 ? 24 : 48, [&](auto F) {
+        hipLaunchKernelGGL((k_poly_syn<F>), gs, blk, 0, s, pa);
+        for_value<1, 2, 3>(ch.ntap == 1 || ch.ntap == 2 ? ch.ntap : 3, [&](auto NT) {
+            hipLaunchKernelGGL((k_poly_chan<F, NT>), gc, blk, 0, s, pa);
+        });
+    });
 }
 
 template <class Out>
 static void launch_poly_ana(hipStream_t s, const SchemeK& sk, const PolyArgs& pa, const Out& o, size_t lds) {
     const dim3 grid((pa.U / WAVE) * pa.K), blk(WAVE);
-    if (sk.poly_F == 24) hipLaunchKernelGGL((k_poly_ana<24, Out>), grid, blk, lds, s, pa, o);
-    else hipLaunchKernelGGL((k_poly_ana<48, Out>), grid, blk, lds, s, pa, o);
+    for_value<24, 48>(sk.poly_F == 24 ? 24 : 48, [&](auto F) {
+        hipLaunchKernelGGL((k_poly_ana<F, Out>), grid, blk, lds, s, pa, o);
+    });
 }
 
 unsigned launch_perfect_ic(hipStream_t s, const Opts& op, const SchemeK& sk, const ChannelK& ch, McBuffers& b,
@@ -3591,55 +3540,20 @@ unsigned launch_perfect_ic(hipStream_t s, const Opts& op, const SchemeK& sk, con
     else launch_band(s, sk.G, b.U, nullptr, LoadSoA{b.u, b.U}, StoreSoA{b.t, b.U});
     // SNR-fastest XCD-aware order: the SNR units of a realisation share its taps
     const BandOrder ord{b.U / WAVE, b.U / b.R, b.R / WAVE, op.xcd};
-    if (!pd) {
-        const StorePerfectIC o{b.yperf, b.y, b.h, b.u, b.U, b.R};
-        if (poly) launch_poly_ana(s, sk, pa, o, 0);
-        else launch_pass2_nt(s, sk, ch, b, ord, o);
+    const auto pass2 = [&](const auto& out, size_t lds) {
+        if (poly) launch_poly_ana(s, sk, pa, out, lds);
+        else launch_pass2_nt(s, sk, ch, b, ord, out, lds);
         return poly ? PATH_PIC_POLY : PATH_PIC_PASSES;
-    }
-    StorePerfectDetect o{};
-    o.y = b.y;
-    o.h = b.h;
-    o.u = b.u;
-    o.sidx = b.sidx;
-    o.row_data = sk.row_data;
-    o.row_cons = sk.row_cons;
-    o.row_pval = sk.row_pval;
-    o.symbols = sk.symbols;
-    o.lvI = sk.lvI;
-    o.lvQ = sk.lvQ;
-    o.grid_sym = sk.grid_sym;
-    o.counters = pd->counters;
-    o.cidx0 = ((((size_t)pd->scheme * 2 + 1) * 2 + 0) * pd->nsnr) * pd->nstage + pd->stage;
-    o.cstride_edge = pd->nsnr * pd->nstage;
-    o.cstride_snr = pd->nstage;
-    o.U = b.U;
-    o.R = b.R;
-    o.rvalid = b.rvalid;
-    o.snr0 = b.snr0;
+    };
+    if (!pd) return pass2(StorePerfectIC{b.yperf, b.y, b.h, b.u, b.U, b.R}, 0);
+    StorePerfectDetect o = detect_operands(sk, b, pd, 1);
+    o.cidx0 += pd->stage;
     o.last = pd->last;
-    o.M = sk.M;
-    o.nI = sk.nI;
-    o.nQ = sk.nQ;
-    o.real_detect = sk.real_detect;
-    o.idd = 1.0 / sk.data_div;
-    o.sI = pd->sI;
-    o.sQ = pd->sQ;
-    o.tr = b.tr;
     o.stage = pd->stage;
     const size_t lds = 256 * sizeof(double2) + sizeof(SlicerLds);
-    const bool bulk = b.tr && b.tr_bulk;
-    const bool bulk_y = bulk && b.tr_yperf;               // ... and y_perf is staged (DSCE_LLR_PERFECT)
-    if (poly) {
-        if (bulk_y) launch_poly_ana(s, sk, pa, StorePerfectDetectBulkY(o), lds);
-        else if (bulk) launch_poly_ana(s, sk, pa, StorePerfectDetectBulk(o), lds);
-        else launch_poly_ana(s, sk, pa, o, lds);
-        return PATH_PIC_POLY;
-    }
-    if (bulk_y) launch_pass2_nt(s, sk, ch, b, ord, StorePerfectDetectBulkY(o), lds);
-    else if (bulk) launch_pass2_nt(s, sk, ch, b, ord, StorePerfectDetectBulk(o), lds);
-    else launch_pass2_nt(s, sk, ch, b, ord, o, lds);
-    return PATH_PIC_PASSES;
+    if (b.bulk_y()) return pass2(StorePerfectDetectBulkY(o), lds);
+    if (b.bulk()) return pass2(StorePerfectDetectBulk(o), lds);
+    return pass2(o, lds);
 }
 
 // ---------------------------------------------------------------------------
@@ -4176,7 +4090,7 @@ unsigned launch_mmse_fused(hipStream_t s, const Opts& op, const SchemeK& sk, con
     fa.scheme = scheme_index;
     fa.rvalid = b.rvalid;
     const dim3 grid(b.U / 64, mm.Pb.nblk);
-    if (b.tr && b.tr_bulk)
+    if (b.bulk())
         hipLaunchKernelGGL(k_wpair3_bulk, grid, dim3(256), 0, s, mm.Pb, mm.Wp3, mm.wp_elems, var_prev, mm.nsnr, b.snr0,
                            b.R, b.U, hp_prev, b.v, b.y, b.yest, sk, fa);
     else
@@ -4190,28 +4104,23 @@ unsigned launch_wcontract(hipStream_t s, const Opts& op, const SchemeK& sk, cons
     // packed band where no pair tiles exist (a block wider than 32 rows) or on
     // request (Opts::wcontract_valu)
     const bool pair_ok = mm.Wp3 && (b.U % 64) == 0 && (b.R % 64) == 0 && !op.wcontract_valu;
+    const int nks = mm.Pb.nks == 2 || mm.Pb.nks == 4 ? mm.Pb.nks : 8;      // k-steps: any other count takes 8
     if (pair_ok && mm.Pb.rbp == 32) {
         // 32-row blocks: one GEMM per row tile, no per-tile epilogue (k_wrow3)
         const dim3 grid(b.U / 64, mm.Pb.nblk);
-#define LAUNCH_WR(NKSV)                                                                                            \
-    hipLaunchKernelGGL((k_wrow3<NKSV>), grid, dim3(256), 0, s, mm.Pb, mm.Wp3, mm.wp_elems, var, mm.nsnr, b.snr0, b.R, \
-                       b.U, b.hp, b.v, b.y, b.yest)
-        if (mm.Pb.nks == 2) LAUNCH_WR(2);
-        else if (mm.Pb.nks == 4) LAUNCH_WR(4);
-        else LAUNCH_WR(8);
-#undef LAUNCH_WR
+        for_value<2, 4, 8>(nks, [&](auto NKS) {
+            hipLaunchKernelGGL((k_wrow3<NKS>), grid, dim3(256), 0, s, mm.Pb, mm.Wp3, mm.wp_elems, var, mm.nsnr, b.snr0,
+                               b.R, b.U, b.hp, b.v, b.y, b.yest);
+        });
         return PATH_WROW3;
     }
     if (pair_ok) {
         // 24-row blocks (PairBand::rbp is 24 or 32)
         const dim3 grid(b.U / 64, mm.Pb.nblk);
-#define LAUNCH_W3(NKSV)                                                                                        \
-    hipLaunchKernelGGL((k_wpair3<24, NKSV, false>), grid, dim3(256), 0, s, mm.Pb, mm.Wp3, mm.wp_elems, var,      \
-                       mm.nsnr, b.snr0, b.R, b.U, b.hp, b.v, b.y, b.yest, sk, FuseArgs{})
-        if (mm.Pb.nks == 2) LAUNCH_W3(2);
-        else if (mm.Pb.nks == 4) LAUNCH_W3(4);
-        else LAUNCH_W3(8);
-#undef LAUNCH_W3
+        for_value<2, 4, 8>(nks, [&](auto NKS) {
+            hipLaunchKernelGGL((k_wpair3<24, NKS, false>), grid, dim3(256), 0, s, mm.Pb, mm.Wp3, mm.wp_elems, var,
+                               mm.nsnr, b.snr0, b.R, b.U, b.hp, b.v, b.y, b.yest, sk, FuseArgs{});
+        });
         return PATH_WPAIR3;
     }
     hipLaunchKernelGGL(k_wcontract_valu, dim3(b.U / WAVE, mm.Wb.nblk), dim3(WAVE), sk.NP * WAVE * sizeof(double2), s,
@@ -4402,21 +4311,14 @@ template <int NPT>
 static void launch_stage_fused_np(hipStream_t s, const SchemeK& sk, const StageArgs& st, const MmseK& mm, McBuffers& b,
                                   unsigned long long* counters) {
     const int ug = b.U / 64, nrb = (sk.LK + 4 * STAGE_RB - 1) / (4 * STAGE_RB);
-#define LAUNCH_SF(PERFV, MSEV)                                                                                \
-    hipLaunchKernelGGL((k_stage_fused<NPT, PERFV, MSEV>), dim3(ug * nrb), dim3(256), 0, s, sk, st, nrb, mm.Wd, b.xp, \
-                       b.sidx, b.h, b.hp, b.hest, b.qe, b.qp, b.v, b.u, counters)
-#define LAUNCH_SFB(PERFV)                                                                                     \
-    hipLaunchKernelGGL((k_stage_fused_bulk<NPT, PERFV, false>), dim3(ug * nrb), dim3(256), 0, s, sk, st, nrb, mm.Wd, b.xp, \
-                       b.sidx, b.h, b.hp, b.hest, b.qe, b.qp, b.v, b.u, counters)
-    if (b.tr && b.tr_bulk) {                                // dsce_export_stages: no MSE sums
-        if (st.perfect) LAUNCH_SFB(true);
-        else LAUNCH_SFB(false);
-    } else if (st.mse_err && st.perfect) LAUNCH_SF(true, true);
-    else if (st.mse_err) LAUNCH_SF(false, true);
-    else if (st.perfect) LAUNCH_SF(true, false);
-    else LAUNCH_SF(false, false);
-#undef LAUNCH_SF
-#undef LAUNCH_SFB
+    const auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(ug * nrb), dim3(256), 0, s, sk, st, nrb, mm.Wd, b.xp, b.sidx, b.h, b.hp, b.hest,
+                           b.qe, b.qp, b.v, b.u, counters);
+    };
+    for_bool(st.perfect != 0, [&](auto PERF) {
+        if (b.bulk()) return launch(k_stage_fused_bulk<NPT, PERF, false>);    // dsce_export_stages: no MSE sums
+        for_bool(st.mse_err != nullptr, [&](auto MSE) { launch(k_stage_fused<NPT, PERF, MSE>); });
+    });
 }
 
 static bool stage_fused_ok(const Opts& op, const SchemeK& sk) {
@@ -4452,16 +4354,15 @@ unsigned launch_stage(hipStream_t s, const Opts& op, const SchemeK& sk, const Mm
     // 3-kernel path)
     if (stage_fused_ok(op, sk)) {
         hipLaunchKernelGGL(k_ls, dim3(b.U / WAVE), dim3(WAVE), 0, s, sk, st, b.xp, b.hp);
-        if (sk.NP == 8) launch_stage_fused_np<8>(s, sk, st, mm, b, counters);
-        else if (sk.NP == 16) launch_stage_fused_np<16>(s, sk, st, mm, b, counters);
-        else launch_stage_fused_np<32>(s, sk, st, mm, b, counters);
+        // (NP is 8, 16 or 32: stage_fused_ok)
+        for_value<8, 16, 32>(sk.NP, [&](auto NP) { launch_stage_fused_np<NP>(s, sk, st, mm, b, counters); });
         if (!last && !sk.p_diag)
             hipLaunchKernelGGL(k_precode, dim3(b.U / WAVE, rblk), dim3(WAVE), 0, s, sk, st, b.xp, b.qe, b.qp, b.v,
                                b.u);
         return PATH_STAGE_FUSED;
     }
     hipLaunchKernelGGL(k_ls, dim3(b.U / WAVE), dim3(WAVE), 0, s, sk, st, b.xp, b.hp);
-    const bool bulk = b.tr && b.tr_bulk;
+    const bool bulk = b.bulk();
     hipLaunchKernelGGL(bulk ? k_ls_hest_bulk : k_ls_hest, dim3(b.U / WAVE, rblk), dim3(WAVE),
                        (size_t)sk.NP * WAVE * sizeof(double2), s, sk, st, mm.Wd, b.h, b.hp, b.e, b.e2);
     hipLaunchKernelGGL(bulk ? k_detect_bulk : k_detect, dim3(b.U / WAVE, (sk.ND + DET_CHUNK - 1) / DET_CHUNK),

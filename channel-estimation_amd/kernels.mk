@@ -3,4 +3,4 @@
 # asan.mk.  Each .hip is its own code object (no -fgpu-rdc).
 KERNELS := kernels_mc kernels_setup kernels_export kernels_llr
 KERNEL_OBJ := $(KERNELS:%=$(ROOT)/build/%.o)
-HDR := $(ROOT)/csrc/dsce_common.h $(ROOT)/csrc/dsce_kernels.h $(ROOT)/csrc/bm_tables.h $(ROOT)/csrc/stage_kernels.inc $(ROOT)/../include/dsce.h
+HDR := $(ROOT)/csrc/dsce_common.h $(ROOT)/csrc/dsce_kernels.h $(ROOT)/csrc/dsce_dispatch.h $(ROOT)/csrc/bm_tables.h $(ROOT)/csrc/stage_kernels.inc $(ROOT)/../include/dsce.h

@@ -376,7 +376,7 @@ def test_batch_invariance_at_full_and_largest_batches():
     8 192 through the bench kernels.  At 262 144 the realisation-major tap
     buffer (ntap N R x 16 B) passes 4 GB, past k_pic_fft's 32-bit buffer view,
     so the engine falls back to the W contraction and the banded perfect-CSI
-    passes (pic_fft_ok / mmse_stages_ok) instead of overflowing; that path
+    passes (perfect_chain_ok / mmse_stages_ok) instead of overflowing; that path
     gives the same counts up to the oracle's borderline decisions (none
     expected)."""
     S = harness.setup("default", schemes=("ofdm",))
