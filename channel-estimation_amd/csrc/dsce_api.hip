@@ -2044,10 +2044,24 @@ Scheme& bulk_export_check(dsce_ctx* ctx, int32_t id, const void* out, uint32_t f
 // show).  launch(bk, snr0): the export kernel of the chunk that starts at SNR
 // index snr0, from the bulk arrays of bk into the sink's out[] at row0, for the
 // sub-batch in ctx->buf (R, rvalid, U).  yperf (DSCE_LLR_PERFECT): y_perf of
-// every stage is staged too, [stage][LK][U], and counts towards the bound.
+// every stage is staged too, [stage][LK][U], and counts towards the bound, as do
+// extra_unit_bytes per unit of a temporary the entry point keeps (dsce_run_coded).
+// Realisations per sub-batch of a bulk export of scheme s: whole waves, at most
+// the batch, such that the bulk trace arrays of a unit (hP, diag(D_hat), y_ic and
+// both decisions of every stage; y_perf too with yperf) plus extra_unit_bytes of
+// the entry point's own stay within export_stage_mb over the chunk's units.
+int bulk_sub_batch(dsce_ctx* ctx, const Scheme& s, bool yperf, size_t extra_unit_bytes) {
+    const size_t LK = s.LK, NP = s.d.n_pilots, ND = s.d.n_data, S = ctx->niter + 1;
+    const size_t unit_bytes =
+        S * ((NP + (yperf ? 3 : 2) * LK) * sizeof(double2) + 2 * ND * sizeof(int)) + extra_unit_bytes;
+    const size_t bound = (size_t)ctx->op.export_stage_mb << 20;
+    const size_t waves = std::max<size_t>(1, bound / (unit_bytes * 64 * (size_t)snr_chunk(ctx)));
+    return (int)std::min<size_t>((size_t)(ctx->batch + 63) / 64, waves) * 64;
+}
+
 template <class Launch>
 void bulk_export(dsce_ctx* ctx, Scheme& s, int32_t id, uint64_t seed, uint64_t first_rep, uint64_t n_rep,
-                 ExportSink& sink, Launch launch, bool yperf = false) {
+                 ExportSink& sink, Launch launch, bool yperf = false, size_t extra_unit_bytes = 0) {
     const std::string w(sink.what);
     sink.check(ctx, [&] {
         if (!(s.mmse_ready && s.Wd))
@@ -2057,13 +2071,8 @@ void bulk_export(dsce_ctx* ctx, Scheme& s, int32_t id, uint64_t seed, uint64_t f
                                             "(n_iter must be 0 with an interpolation estimator)");
     });
     const int LK = s.LK, NP = s.d.n_pilots, ND = s.d.n_data, nsnr = ctx->nsnr, S = ctx->niter + 1;
-    // the bulk trace arrays of one unit: hP, diag(D_hat), y_ic and both decisions of every stage
     const int chunk = snr_chunk(ctx);
-    const size_t unit_bytes =
-        (size_t)S * (((size_t)NP + (yperf ? 3 : 2) * (size_t)LK) * sizeof(double2) + 2 * (size_t)ND * sizeof(int));
-    const size_t bound = (size_t)ctx->op.export_stage_mb << 20;
-    const size_t waves = std::max<size_t>(1, bound / (unit_bytes * 64 * (size_t)chunk));
-    const int rsub = (int)std::min<size_t>((size_t)(ctx->batch + 63) / 64, waves) * 64;
+    const int rsub = bulk_sub_batch(ctx, s, yperf, extra_unit_bytes);
     DeviceTemps tmp(ctx);
     Bulk bk;
     bk.scheme = id;
@@ -3035,6 +3044,129 @@ int dsce_run_calib(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep,
         for (size_t i = 0; i < n_perf; ++i) out->ratio_perf0[i] += host[n_est + i];
     }
     tmp.release_checked();
+    API_END
+}
+
+// The checks of a code table against n_slots slots (dsce_run_coded, dsce_viterbi)
+static void check_code(const dsce_code_desc* code, int64_t n_slots, const std::string& w) {
+    if (!code || !code->src) throw ApiError(DSCE_EINVAL, w + ": null code or src");
+    if (code->n_steps < 1) throw ApiError(DSCE_EINVAL, w + ": n_steps < 1");
+    if (code->terminated && code->n_steps < 7)
+        throw ApiError(DSCE_EINVAL, w + ": a terminated code needs n_steps >= 7 (six tail zeros)");
+    if (code->n_steps > DSCE_CODE_MAX_STEPS)
+        throw ApiError(DSCE_EINVAL, w + ": n_steps > DSCE_CODE_MAX_STEPS (8192)");
+    static_assert(DSCE_CODE_MAX_STEPS == CODE_MAX_STEPS, "header and kernel limit");
+    for (size_t i = 0; i < 2 * (size_t)code->n_steps; ++i)
+        if (code->src[i] < -1 || (int64_t)code->src[i] >= n_slots)
+            throw ApiError(DSCE_EINVAL, w + ": src entry outside [-1, slots)");
+}
+
+// Coded bit and frame errors (DSCE_HAS_CODED_RUN): dsce_run_soft's run with a
+// decoder in place of the sum.  After each SNR chunk k_llr, unmodified and in its
+// fp64 instance with llr only, writes the chunk's LLRs into a device temporary in
+// the export layout, [rsub][n_snr][S][ND m] with row0 = 0 (k_llr indexes by the
+// absolute SNR index, so the temporary has every SNR row; its bytes per unit count
+// towards export_stage_mb): the bits of dsce_export_llr.  k_viterbi then decodes
+// one codeword per wave and adds its counts to int64 device accumulators that live
+// for the call (declared before bulk_export's temporaries, so they outlive its
+// stream wait); they are added into the caller's arrays once.
+int dsce_run_coded(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, uint64_t n_rep, uint32_t flags,
+                   const dsce_code_desc* code, const dsce_coded_out* out) {
+    TraceRange trace_range("dsce run coded");
+    API_BEGIN
+    check_ctx(ctx);
+    Scheme& s = bulk_export_check(ctx, id, out, flags, DSCE_LLR_MAXLOG | DSCE_LLR_PERFECT, "dsce_run_coded");
+    const bool perfect = (flags & DSCE_LLR_PERFECT) != 0, maxlog = (flags & DSCE_LLR_MAXLOG) != 0;
+    const int ND = s.d.n_data, nsnr = ctx->nsnr, S = ctx->niter + 1, m = s.d.bits_per_symbol;
+    const size_t B = (size_t)ND * m;
+    check_code(code, (int64_t)B, "dsce_run_coded");
+    ExportSink sink{"dsce_run_coded", 2, {out->bit_err, out->frame_err}, {0, 0}, {sizeof(int64_t), sizeof(int64_t)}, false};
+    const size_t ncell = (size_t)nsnr * S;
+    const bool any = out->bit_err || out->frame_err;
+    const int chunk = snr_chunk(ctx);
+    const size_t extra = (S * B * sizeof(double) * (size_t)nsnr + chunk - 1) / chunk;
+    const int rsub = bulk_sub_batch(ctx, s, perfect, extra);
+    std::vector<unsigned long long> host(2 * ncell);
+    DeviceTemps tmp(ctx);
+    CodedK q{};
+    double* dllr = nullptr;
+    if (any) {
+        // no field requested: bulk_export refuses below, before anything is launched
+        unsigned long long* acc = tmp.alloc<unsigned long long>(2 * ncell);
+        DSCE_HIP_CHECK(hipMemsetAsync(acc, 0, 2 * ncell * sizeof(unsigned long long), ctx->stream));
+        q.acc_bit = out->bit_err ? acc : nullptr;
+        q.acc_frame = out->frame_err ? acc + ncell : nullptr;
+        int* dsrc = tmp.alloc<int>(2 * (size_t)code->n_steps);
+        DSCE_HIP_CHECK(hipMemcpyAsync(dsrc, code->src, 2 * (size_t)code->n_steps * sizeof(int), hipMemcpyHostToDevice,
+                                      ctx->stream));
+        q.src = dsrc;
+        if (n_rep > 0) dllr = tmp.alloc<double>((size_t)rsub * nsnr * S * B);
+    }
+    q.T = code->n_steps;
+    q.terminated = code->terminated ? 1 : 0;
+    q.wpb = viterbi_waves_per_block(q.T);
+    q.m = m;
+    q.B = (int)B;
+    q.S = S;
+    q.nsnr = nsnr;
+    bulk_export(ctx, s, id, seed, first_rep, n_rep, sink, [&](const Bulk& bk, int snr0) {
+        LlrK a = llr_args(ctx, s, bk, snr0, maxlog, perfect);
+        if (a.R > rsub || a.rvalid > a.R) throw ApiError(DSCE_EINVAL, "dsce_run_coded: LLR temporary too small");
+        a.row0 = 0;
+        a.out[2] = dllr;
+        {
+            Timed t(ctx, "k_llr");
+            launch_llr(ctx->stream, a, false);
+        }
+        q.llr = dllr;
+        q.sidx = ctx->buf.sidx;
+        q.R = a.R;
+        q.snr0 = snr0;
+        q.nchunk = a.U / a.R;
+        q.ncw = (long long)a.rvalid * q.nchunk * S;
+        Timed t(ctx, "k_viterbi");
+        launch_viterbi(ctx->stream, q);
+        DSCE_HIP_CHECK(hipGetLastError());
+    }, perfect, extra);
+    if (n_rep > 0 && any) {
+        const unsigned long long* from = q.acc_bit ? q.acc_bit : q.acc_frame - ncell;
+        DSCE_HIP_CHECK(hipMemcpyAsync(host.data(), from, host.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                                      ctx->stream));
+        DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        for (size_t i = 0; out->bit_err && i < ncell; ++i) out->bit_err[i] += (int64_t)host[i];
+        for (size_t i = 0; out->frame_err && i < ncell; ++i) out->frame_err[i] += (int64_t)host[ncell + i];
+    }
+    tmp.release_checked();
+    API_END
+}
+
+// The decoder of dsce_run_coded on the caller's lam: k_viterbi_probe, the same
+// device function with another load and store.  Needs only the context.
+int dsce_viterbi(dsce_ctx* ctx, const dsce_code_desc* code, int64_t n_slots, const double* lam, int64_t n_cw,
+                 uint8_t* info_out) {
+    API_BEGIN
+    check_ctx(ctx);
+    if (n_slots < 0) throw ApiError(DSCE_EINVAL, "dsce_viterbi: n_slots < 0");
+    check_code(code, n_slots, "dsce_viterbi");
+    if (n_cw < 0) throw ApiError(DSCE_EINVAL, "dsce_viterbi: n_cw < 0");
+    if (n_cw > 0 && (!lam || !info_out)) throw ApiError(DSCE_EINVAL, "dsce_viterbi: null pointer");
+    if (n_cw > 0) {
+        const size_t T = (size_t)code->n_steps, nl = (size_t)n_cw * (size_t)n_slots;
+        DeviceTemps tmp(ctx);
+        int* dsrc = tmp.alloc<int>(2 * T);
+        double* dlam = tmp.alloc<double>(nl);
+        uint8_t* dout = tmp.alloc<uint8_t>((size_t)n_cw * T);
+        DSCE_HIP_CHECK(hipMemcpyAsync(dsrc, code->src, 2 * T * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        if (nl) DSCE_HIP_CHECK(hipMemcpyAsync(dlam, lam, nl * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        {
+            Timed t(ctx, "k_viterbi");
+            launch_viterbi_probe(ctx->stream, dsrc, (int)T, code->terminated ? 1 : 0, n_cw, n_slots, dlam, dout);
+        }
+        DSCE_HIP_CHECK(hipGetLastError());
+        DSCE_HIP_CHECK(hipMemcpyAsync(info_out, dout, (size_t)n_cw * T, hipMemcpyDeviceToHost, ctx->stream));
+        tmp.release_checked();
+        if (ctx->timing) collect_timing(ctx);
+    }
     API_END
 }
 

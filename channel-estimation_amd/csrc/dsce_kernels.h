@@ -409,6 +409,32 @@ struct LlrCalibK {
     double* acc_perf;         // [nsnr][ND], or null
 };
 void launch_llr_calib(hipStream_t s, const LlrCalibK& a);
+// K = 7 Viterbi decoder of one sub-batch and SNR chunk after k_llr (k_viterbi,
+// kernels_viterbi.hip; dsce_run_coded): one wave per codeword = (realisation rl <
+// rvalid, SNR point of the chunk, stage), ncw = rvalid nchunk S of them, stage
+// fastest.  llr is k_llr's fp64 output with row0 = 0, [R][nsnr][S][B], B = ND m;
+// the decoder input of slot j m + b is that LLR, negated where bit b of
+// sidx[j][rl] is 1.  src [T][2] holds slots in [-1, B) (checked by the host).  The
+// decoded ones among the first T - 6 (terminated) or T inputs are added to
+// acc_bit[snr][stage], and 1 to acc_frame[snr][stage] if there are any, with
+// integer atomics.  wpb waves per block, each with T decision words of LDS.
+struct CodedK {
+    const int* src;           // [T][2]
+    int T, terminated, wpb;
+    long long ncw;
+    const double* llr;        // [R][nsnr][S][B]
+    const uint16_t* sidx;     // [ND][R] transmitted symbol indices
+    int m, B, S, R, nsnr, snr0, nchunk;
+    unsigned long long* acc_bit;     // [nsnr][S], or null
+    unsigned long long* acc_frame;   // [nsnr][S], or null
+};
+constexpr int CODE_MAX_STEPS = 8192;  // DSCE_CODE_MAX_STEPS: 8 bytes of decisions per step, 64 KiB per block
+inline int viterbi_waves_per_block(int T) { return std::max(1, std::min(4, CODE_MAX_STEPS / std::max(T, 1))); }
+inline size_t viterbi_lds(int T, int wpb) { return (size_t)T * wpb * sizeof(unsigned long long); }
+void launch_viterbi(hipStream_t s, const CodedK& a);
+// the same decoder on lam [ncw][n_slots]: every decoded input to out [ncw][T] (k_viterbi_probe; dsce_viterbi)
+void launch_viterbi_probe(hipStream_t s, const int* src, int T, int terminated, long long ncw, long long n_slots,
+                          const double* lam, uint8_t* out);
 // LLRs of n points x (pn: one value or one per point), out [n][m]
 void launch_llr_probe(hipStream_t s, const LlrTab& t, const double2* x, const double* pn, long long n_pn, long long n,
                       bool maxlog, double* out);

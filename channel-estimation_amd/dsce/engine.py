@@ -30,6 +30,7 @@ EXPORTED = [
     "dsce_llr_awgn", "dsce_export_llr", "dsce_llr_info", "dsce_run_soft",
     "dsce_run_calib", "dsce_set_llr_scale", "dsce_get_llr_scale",
     "dsce_set_llr_scale_perf", "dsce_get_llr_scale_perf",
+    "dsce_run_coded", "dsce_viterbi",
 ]
 
 ABI_VERSION = 10
@@ -117,6 +118,14 @@ class CalibOut(C.Structure):
     _fields_ = [("ratio_est", C.POINTER(C.c_double)), ("ratio_perf0", C.POINTER(C.c_double))]
 
 
+class CodeDesc(C.Structure):
+    _fields_ = [("n_steps", C.c_int32), ("terminated", C.c_int32), ("src", C.POINTER(C.c_int32))]
+
+
+class CodedOut(C.Structure):
+    _fields_ = [("bit_err", C.POINTER(C.c_int64)), ("frame_err", C.POINTER(C.c_int64))]
+
+
 class TxDesc(C.Structure):
     _fields_ = [("kind", C.c_int32), ("n_subcarriers", C.c_int32), ("n_symbols", C.c_int32),
                 ("n_samples", C.c_int32), ("fft_size", C.c_int32), ("intermediate_bin", C.c_int32),
@@ -193,6 +202,9 @@ def load_library(path=None):
     lib.dsce_get_llr_scale.argtypes = [vp, C.c_int32, dp, dp, C.POINTER(C.c_int32)]
     lib.dsce_set_llr_scale_perf.argtypes = [vp, C.c_int32, dp]
     lib.dsce_get_llr_scale_perf.argtypes = [vp, C.c_int32, dp, C.POINTER(C.c_int32)]
+    lib.dsce_run_coded.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                   C.POINTER(CodeDesc), C.POINTER(CodedOut)]
+    lib.dsce_viterbi.argtypes = [vp, C.POINTER(CodeDesc), C.c_int64, dp, C.c_int64, C.POINTER(C.c_uint8)]
     for name in EXPORTED:
         fn = getattr(lib, name)
         if name != "dsce_last_error":
@@ -691,6 +703,64 @@ class Engine:
         set1 = (C.c_int32 * 1)()
         self._chk(self.lib.dsce_get_llr_scale_perf(self.h, int(sid), _dptr(g_perf), set1), "dsce_get_llr_scale_perf")
         return dict(g_perf=g_perf, set=bool(set1[0]))
+
+    # -- coded BER from a K = 7 Viterbi decoder (DSCE_HAS_CODED_RUN) -------------------
+    @staticmethod
+    def _code_desc(code):
+        """(CodeDesc, the int32 table it points to) of a dsce.coding.Code"""
+        src = np.ascontiguousarray(code.src, dtype=np.int32)
+        if src.ndim != 2 or src.shape[1] != 2:
+            raise ValueError("code.src must be [n_steps][2]")
+        return CodeDesc(int(src.shape[0]), int(bool(code.terminated)), src.ctypes.data_as(C.POINTER(C.c_int32))), src
+
+    def viterbi(self, lam, code):
+        """The engine's decoder on caller-supplied lam [n_cw][n_slots] (or [n_slots];
+        positive = the bit is 1) under the table of `code` (dsce.coding.make_code):
+        uint8 [n_cw][n_steps] decoded inputs (dsce_viterbi), equal to the bit to
+        dsce.coding.viterbi_decode.  Needs only the context."""
+        lam = np.asarray(lam, dtype=np.float64)
+        single = lam.ndim == 1
+        lam = np.ascontiguousarray(lam.reshape(-1, lam.shape[-1]))
+        desc, src = self._code_desc(code)
+        out = np.zeros((lam.shape[0], src.shape[0]), dtype=np.uint8)
+        self._chk(self.lib.dsce_viterbi(self.h, C.byref(desc), lam.shape[1], _dptr(lam), lam.shape[0],
+                                        out.ctypes.data_as(C.POINTER(C.c_uint8))), "dsce_viterbi")
+        return out[0] if single else out
+
+    def coded_shapes(self, sid):
+        """Shapes of dsce_run_coded's arrays for scheme sid."""
+        d = self.scheme_dims(sid)
+        return dict(bit_err=(d.n_snr, d.n_iter + 1), frame_err=(d.n_snr, d.n_iter + 1))
+
+    def run_coded(self, sid, seed, first_rep, n_rep, code, method="exact", out=None, branch="mmse"):
+        """Decoded-error counts of the K = 7 convolutional code of `code`
+        (dsce.coding.make_code(ND m, rate)) over the LLRs that export_llr would
+        return for realisations [first_rep, first_rep + n_rep) of scheme sid, one
+        codeword per realisation, SNR point and stage, decoded on the GPU
+        (dsce_run_coded): dict of int64 arrays bit_err and frame_err [n_snr][S].
+        The all-zero information word is simulated under the BITS stream as the
+        scrambler, which is exact for a linear code (include/dsce.h).  The counts
+        are ADDED into the arrays of `out` (a dict with either or both keys,
+        C-contiguous int64; only the given ones are computed) and `out` is
+        returned; without it both are computed from zero.  BER = bit_err / (n_rep
+        code.n_info), FER = frame_err / n_rep.  branch 'perfect'
+        (DSCE_LLR_PERFECT): the LLRs of the perfect-CSI branch."""
+        shapes = self.coded_shapes(sid)
+        if out is None:
+            out = {f: np.zeros(shp, dtype=np.int64) for f, shp in shapes.items()}
+        o = CodedOut()
+        for f, a in out.items():
+            if f not in shapes:
+                raise ValueError("unknown coded output %r (of %s)" % (f, list(shapes)))
+            if not (isinstance(a, np.ndarray) and a.dtype == np.int64 and a.flags.c_contiguous
+                    and a.shape == shapes[f]):
+                raise ValueError("%s must be a C-contiguous int64 array of shape %s" % (f, shapes[f]))
+            setattr(o, f, a.ctypes.data_as(C.POINTER(C.c_int64)))
+        desc, src = self._code_desc(code)
+        self._chk(self.lib.dsce_run_coded(self.h, int(sid), int(seed), int(first_rep), int(n_rep),
+                                          self._llr_flag(method) | self._branch_flag(branch), C.byref(desc),
+                                          C.byref(o)), "dsce_run_coded")
+        return out
 
     # -- engine state ------------------------------------------------------------
     def scheme_dims(self, sid):

@@ -70,6 +70,14 @@ def main(argv=None):
                          "scale pn_eff by it (dsce_set_llr_scale, dsce_set_llr_scale_perf) and "
                          "report the rate of the scaled LLRs too.  rho is in-sample: the calibrated rate is biased "
                          "upward by O(1 / reps), so a sweep wants thousands of realisations")
+    ap.add_argument("--coded", choices=("1/2", "2/3", "3/4", "5/6"), default=None, metavar="RATE",
+                    help="also the coded bit and frame error rate per scheme, SNR point and IC stage: the K = 7 "
+                         "convolutional code (133, 171) punctured to RATE (1/2, 2/3, 3/4, 5/6), one codeword per "
+                         "realisation over a random interleaver, decoded on the GPU from the demapper's LLRs "
+                         "(dsce_run_coded; exact LLRs, or --rate's method), MMSE and perfect-CSI branch.  With "
+                         "--calibrate it runs after the scale tables are installed")
+    ap.add_argument("--coded-interleaver", type=int, default=7, metavar="SEED",
+                    help="with --coded: the interleaver is numpy.random.RandomState(SEED).permutation(ND m)")
     a = ap.parse_args(argv)
     if (a.resume or a.stop_after is not None) and not a.checkpoint:
         raise SystemExit("--resume / --stop-after need --checkpoint")
@@ -83,6 +91,14 @@ def main(argv=None):
                          (a.config == "doubly_flat", "--config doubly_flat (its own simulator)")):
             if on:
                 raise SystemExit("--rate cannot be combined with " + what)
+    if a.coded:
+        # like the rate pass: one plain sweep of the rank's realisations after the counters
+        for on, what in ((a.checkpoint, "--checkpoint (the coded counts are not checkpointed)"),
+                         (a.shard == "snr", "--shard snr (the coded pass runs every SNR point of the engine)"),
+                         (a.devices, "--devices (dsce_run_coded is member 0's on a multi-device context)"),
+                         (a.config == "doubly_flat", "--config doubly_flat (its own simulator)")):
+            if on:
+                raise SystemExit("--coded cannot be combined with " + what)
 
     from dsce import results
     from dsce.configs import build_setup
@@ -142,6 +158,9 @@ def main(argv=None):
     closs_e, closs_p = np.zeros_like(loss_e), np.zeros_like(loss_p)
     ratio_pi = [np.zeros((nsnr, nst, nd)) for nd in n_data]
     closs_pi = np.zeros_like(loss_e)
+    # --coded: [scheme][branch: mmse, perfect][field: bit_err, frame_err][snr][stage]
+    coded = np.zeros((len(names), 2, 2, nsnr, nst), dtype=np.int64)
+    codes, coded_s = [], 0.0
     eng = None
     setup_s, t0 = 0.0, time.perf_counter()
     ck_path = None
@@ -229,6 +248,19 @@ def main(argv=None):
             for at in range(0, mine, step):
                 eng.run_soft(i, a.seed, first + at, min(step, mine - at), a.rate, out, branch="perfect")
         rate_s += time.perf_counter() - t1
+    if a.coded:
+        # one dsce_run_coded pass per scheme and branch over the same realisations, after --calibrate's tables
+        from dsce.coding import make_code
+        t1 = time.perf_counter()
+        for i, s in enumerate(names):
+            sc = S.schemes[s]
+            codes.append(make_code(int(sc.n_data) * int(sc.bits_per_symbol), a.coded, interleaver=a.coded_interleaver))
+            for b, branch in enumerate(("mmse", "perfect") if mine else ()):
+                out = {"bit_err": coded[i, b, 0], "frame_err": coded[i, b, 1]}
+                for at in range(0, mine, step):
+                    eng.run_coded(i, a.seed, first + at, min(step, mine - at), codes[i], a.rate or "exact", out,
+                                  branch=branch)
+        coded_s = time.perf_counter() - t1
     if eng is not None:
         eng.close()
     complete = done >= mine
@@ -250,7 +282,7 @@ def main(argv=None):
             dist.destroy_process_group()
         return 0
     # "seconds" is the counter loop's: the rate pass is timed on its own
-    extra = {"setup_s": setup_s, "seconds": prior_s + time.perf_counter() - t0 - rate_s, "ranks": world,
+    extra = {"setup_s": setup_s, "seconds": prior_s + time.perf_counter() - t0 - rate_s - coded_s, "ranks": world,
              "shard": a.shard}
     if a.rate:
         extra["bicm_rate_seconds"] = rate_s
@@ -270,6 +302,8 @@ def main(argv=None):
             loss_e = allreduce_counts(loss_e, dev)
             loss_p = allreduce_counts(loss_p, dev)
             loss_pi = allreduce_counts(loss_pi, dev)
+        if a.coded:
+            coded = allreduce_counts(coded, dev)
         if a.calibrate:
             closs_e = allreduce_counts(closs_e, dev)
             closs_p = allreduce_counts(closs_p, dev)
@@ -320,6 +354,18 @@ def main(argv=None):
                                     "perfect_ic": {e: (ratio_pi[i][:, :, sel[k]].mean(axis=-1) / reps).tolist()
                                                    for k, e in enumerate(EDGE)}},
                     "calibration": {"reps": int(reps), "in_sample": True}})
+    if a.coded:
+        # BER = bit_err / (reps info_bits), FER = frame_err / reps: one codeword per realisation (include/dsce.h)
+        extra["coded_seconds"] = coded_s
+        extra["coded"] = {}
+        for i, s in enumerate(names):
+            k = codes[i].n_info
+            extra["coded"][s] = {"rate": a.coded, "info_bits": int(k), "steps": int(codes[i].n_steps),
+                                 "interleaver": int(a.coded_interleaver), "method": a.rate or "exact",
+                                 "calibrated": bool(a.calibrate)}
+            for b, branch in enumerate(("mmse", "perfect_ic")):
+                extra["coded"][s][branch] = {"ber": (coded[i, b, 0] / (float(reps) * k)).tolist(),
+                                             "fer": (coded[i, b, 1] / float(reps)).tolist()}
     extra["realisations_per_s"] = reps / extra["seconds"]
     res = results.make(S, names, counts, bits, reps, a.seed, extra=extra)
     if rank != 0:
@@ -346,6 +392,13 @@ def main(argv=None):
                               **({"bicm_rate_ic_mmse_calibrated": r["mmse_calibrated"]["all"][k][-1]}
                                  if a.calibrate else {})}
                           for s, r in extra["bicm_rate"].items()}))
+    if a.coded:
+        print(json.dumps({s: {"snr_db": float(S.snr_db[k]), "rate": r["rate"], "info_bits": r["info_bits"],
+                              "coded_ber_ic_mmse": r["mmse"]["ber"][k][-1],
+                              "coded_ber_onetap_mmse": r["mmse"]["ber"][k][0],
+                              "coded_fer_ic_mmse": r["mmse"]["fer"][k][-1],
+                              "coded_ber_ic_perfect": r["perfect_ic"]["ber"][k][-1]}
+                          for s, r in extra["coded"].items()}))
     if distributed:
         dist.destroy_process_group()
     return 0

@@ -43,6 +43,9 @@
  *                            against the BITS stream, summed per SNR point and stage
  *   dsce_run_calib        <- no counterpart in the script: the demapper error against the
  *                            transmitted symbols over pn_eff, per position
+ *   dsce_run_coded        <- no counterpart in the script: the bit and frame errors of a
+ *                            K = 7 Viterbi decoder fed with those LLRs, per SNR point and stage
+ *   dsce_viterbi          <- the same decoder on the caller's own decoder input
  *
  * Conventions
  *  - Return 0 on success, a negative DSCE_E* code on failure; the message is
@@ -98,6 +101,8 @@
  * DSCE_HAS_LLR_PERFECT (still ABI 10) announces the flag DSCE_LLR_PERFECT of
  * dsce_export_llr, dsce_run_soft and dsce_run_calib (the perfect-CSI branch at
  * every stage) with dsce_set_llr_scale_perf and dsce_get_llr_scale_perf.
+ * DSCE_HAS_CODED_RUN (still ABI 10) announces dsce_run_coded and dsce_viterbi:
+ * the coded bit and frame errors of a K = 7 Viterbi decoder on the device.
  */
 #ifndef DSCE_H
 #define DSCE_H
@@ -692,6 +697,98 @@ int dsce_set_llr_scale_perf(dsce_ctx* ctx, int32_t scheme_id, const double* g_pe
 /* set1[0] = 1 where g_perf is installed; the table is copied out, 1.0 everywhere
  * when it is not.  Every pointer optional.  DSCE_ESTATE before dsce_set_snr. */
 int dsce_get_llr_scale_perf(dsce_ctx* ctx, int32_t scheme_id, double* g_perf, int32_t* set1);
+
+/* ---- coded BER from a K = 7 Viterbi decoder (DSCE_HAS_CODED_RUN; additive,
+ *      ABI 10) -------------------------------------------------------------- */
+/* Definitions.
+ *  Code: rate 1/2, constraint length 7.  Input u_t, with u_t = 0 for t < 0; the
+ *  two outputs of trellis step t are
+ *    o0 = u_t ^ u_{t-2} ^ u_{t-3} ^ u_{t-5} ^ u_{t-6}   (133 octal)
+ *    o1 = u_t ^ u_{t-1} ^ u_{t-2} ^ u_{t-3} ^ u_{t-6}   (171 octal);
+ *  the free distance is 10.
+ *  State: s holds u_{t-1} in bit 0 through u_{t-6} in bit 5.  The next state is
+ *  ns = ((s << 1) | u_t) & 63; the predecessors of ns are p_b = (ns >> 1) | (b << 5)
+ *  for b = 0, 1, with input u_t = ns & 1.
+ *  Slots: a realisation offers B = ND m coded-bit slots; slot j m + b is bit b of
+ *  data symbol j, the [ND][m] flattening of llr in dsce_export_llr.
+ *  Code table: src[T][2] gives, for step t and output k, the slot that carries
+ *  it, or -1 for a punctured output, which contributes 0.  Interleaving and
+ *  puncturing are nothing but this table; the host builds it (dsce/coding.py
+ *  make_code: rates 1/2, 2/3, 3/4 and 5/6 with a random interleaver) and the
+ *  engine does not know about rates.
+ *  Decoder input:
+ *    lam[i]  = t_i ? -LLR_i : LLR_i, t_i the transmitted bit of slot i (bit b of
+ *              sym[rep][j], the sym of dsce_export): positive means "the
+ *              descrambled bit is 1";
+ *    z_{t,k} = src[t][k] < 0 ? 0.0 : lam[src[t][k]].
+ *  Why this is exact.  The engine does not encode: it simulates the all-zero
+ *  codeword under the scrambler t, the BITS stream, which is uniformly random.
+ *  The physical transmission depends only on t = c ^ s, with c the codeword and s
+ *  the scrambler.  A maximum-likelihood sequence decoder maximises
+ *  sum_i (1 - 2 e_i)(1 - 2 t_i) LLR_i over the codewords e = c_hat ^ c (the code is
+ *  linear, so e runs over the code as c_hat does).  So the error pattern e depends
+ *  only on lam and is independent of c: the decoded information bits of the
+ *  all-zero codeword that are not 0 are the bit errors of any codeword sent with
+ *  that scrambler.
+ *  Decoder (fp64, exactly this order; dsce/coding.py viterbi_decode is the
+ *  bit-identical NumPy twin):
+ *   1. pm[0] = 0 and pm[s] = -inf otherwise.
+ *   2. Per step and next state ns: c_b = (pm[p_b] + (o0(p_b, u) ? z_{t,0} : 0.0))
+ *      + (o1(p_b, u) ? z_{t,1} : 0.0), b = 0, 1, u = ns & 1.
+ *   3. The decision is d = (c_1 > c_0): a tie, and -inf against -inf, choose b = 0.
+ *   4. pm[ns] = d ? c_1 : c_0.  No renormalisation.
+ *   5. Traceback starts from state 0 if `terminated`, else from the state of
+ *      largest pm, lowest index on ties.
+ *   6. The decoded u_t is bit 0 of the state after step t.
+ *  Counts: K = T - 6 information bits if `terminated` (the last six inputs are tail
+ *  zeros), else K = T; bit_err = the number of decoded u_t = 1 for t < K;
+ *  frame_err = 1 if bit_err is non-zero.  One codeword per realisation, SNR point
+ *  and stage; BER = bit_err / (n_rep K), FER = frame_err / n_rep.
+ *  Not built: other codes, both branches in one call, sharding over a
+ *  multi-device handle. */
+#define DSCE_HAS_CODED_RUN 1
+#define DSCE_CODE_MAX_STEPS 8192   /* the decision words of a codeword (8 bytes per step) stay within 64 KiB of LDS */
+typedef struct {
+    int32_t n_steps;        /* T: 1 .. DSCE_CODE_MAX_STEPS, at least 7 if terminated */
+    int32_t terminated;     /* 1: the last six inputs are tail zeros, traceback from state 0 */
+    const int32_t* src;     /* [n_steps][2] slot of output k of step t, or -1 (punctured) */
+} dsce_code_desc;
+
+typedef struct {            /* each optional */
+    int64_t* bit_err;       /* [n_snr][1 + n_iter] */
+    int64_t* frame_err;     /* [n_snr][1 + n_iter] */
+} dsce_coded_out;
+
+/* ADDS the counts defined above into the caller's int64 host arrays, as dsce_run
+ * adds into err_counts.  The run is dsce_run_soft's with a decoder in place of
+ * the sum (the same realisations for the same seed; batches, SNR chunks, the
+ * export_stage_mb cut, padding realisations that count nowhere, any n_rep >= 0
+ * with n_rep = 0 adding nothing, no change to the error counters, the MSE sums or
+ * dsce_path_info): after each SNR chunk "k_llr" writes the fp64 LLRs of the chunk
+ * into a device temporary in the layout of dsce_export_llr (its bytes count
+ * towards export_stage_mb), so they are the bits dsce_export_llr exports for the
+ * same flags, installed scale tables included (g_est, or g_perf with
+ * DSCE_LLR_PERFECT); then "k_viterbi" (its name under dsce_enable_timing) decodes
+ * one codeword per wavefront, lane = state, and adds its counts to device int64
+ * accumulators that live for the call.  Integers: any order of summation gives
+ * the same counts, and two identical calls return identical counts.  flags: 0 |
+ * DSCE_LLR_MAXLOG | DSCE_LLR_PERFECT; any other bit is DSCE_EINVAL, as are a null
+ * code or src, n_steps < 1, terminated with n_steps < 7, n_steps >
+ * DSCE_CODE_MAX_STEPS, a src entry outside [-1, ND m), a null out and no field
+ * requested.  DSCE_ESTATE as for dsce_run_soft.  On a multi-device handle the
+ * call is member 0's. */
+int dsce_run_coded(dsce_ctx* ctx, int32_t scheme_id, uint64_t seed, uint64_t first_rep, uint64_t n_rep,
+                   uint32_t flags, const dsce_code_desc* code, const dsce_coded_out* out);
+
+/* The same decoder (the device function of dsce_run_coded, with another load and
+ * store) for caller-supplied lam [n_cw][n_slots]: nothing is descrambled, and any
+ * codeword is decoded.  info_out [n_cw][n_steps]: all n_steps decoded inputs of
+ * every codeword, 0 / 1.  Needs only a context: no scheme, channel or SNR point
+ * has to be set.  DSCE_EINVAL for the code errors above (src entries in [-1,
+ * n_slots)), n_slots < 0, n_cw < 0 and null data pointers with n_cw > 0; n_cw = 0
+ * does nothing. */
+int dsce_viterbi(dsce_ctx* ctx, const dsce_code_desc* code, int64_t n_slots, const double* lam, int64_t n_cw,
+                 uint8_t* info_out);
 
 /* ---- engine state ------------------------------------------------------- */
 int dsce_scheme_dims(dsce_ctx* ctx, int32_t scheme_id, dsce_dims* dims);
