@@ -729,7 +729,12 @@ int dsce_get_llr_scale_perf(dsce_ctx* ctx, int32_t scheme_id, double* g_perf, in
  *  linear, so e runs over the code as c_hat does).  So the error pattern e depends
  *  only on lam and is independent of c: the decoded information bits of the
  *  all-zero codeword that are not 0 are the bit errors of any codeword sent with
- *  that scrambler.
+ *  that scrambler.  "Exact" holds where the maximum-likelihood path is unique.  At
+ *  an exact tie of two path metrics the fixed tie rule below favours one path by
+ *  its labels (b = 0, the lowest state), not by its metric, and which codeword
+ *  that is depends on c; for LLRs of a continuous channel such ties have
+ *  negligible probability.  lam is expected to be finite: a NaN loses every
+ *  comparison, so a codeword with one decodes as "no error".
  *  Decoder (fp64, exactly this order; dsce/coding.py viterbi_decode is the
  *  bit-identical NumPy twin):
  *   1. pm[0] = 0 and pm[s] = -inf otherwise.

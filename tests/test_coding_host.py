@@ -3,8 +3,11 @@ DSCE_HAS_CODED_RUN) — dsce.coding: the K = 7 code (133, 171), the code tables
 (puncturing and interleaving), the NumPy twin of k_viterbi, its error correction
 over BPSK / AWGN, the header's declarations against the ctypes binding, and the
 conventions pinned on the oracle's LLRs: the decoded-error counts of the default
-OFDM scheme recorded from a prototype of the definitions of include/dsce.h.  No
-GPU call; tests/test_gpu_coded.py compares the engine against this twin."""
+OFDM scheme recorded from a prototype of the definitions of include/dsce.h, and
+the same counts from random codewords in place of the all-zero one.  No GPU
+call; tests/test_gpu_coded.py compares the engine against this twin, and
+tests/test_coding_ml_host.py compares the twin with references that are not a
+decoder."""
 import ctypes
 import itertools
 import os
@@ -194,6 +197,33 @@ def test_conventions_pinned_on_the_oracle(oracle_llr, rate):
     sym = (bits.reshape(n, nd, m).astype(np.int64) << np.arange(m)).sum(axis=-1)
     cc = coded_counts(llr, sym, code)
     assert np.array_equal(cc["bit_err"], bit) and np.array_equal(cc["frame_err"], frame)
+
+
+@pytest.mark.parametrize("terminated", [True, False])
+@pytest.mark.parametrize("rate", ["3/4", "1/2"])
+def test_oracle_counts_with_real_codewords(oracle_llr, rate, terminated):
+    """The counts without the all-zero shortcut: a random information word per
+    (realisation, SNR point, stage) is encoded, lam = (1 - 2 t) LLR gets the sign
+    of its coded bits, and the decoded word is compared with the one sent.  Per
+    row the number of wrong information bits is that of the all-zero word, so the
+    terminated tables give ORACLE_COUNTS again; the oracle's |lam| spans ten
+    decades and is not rounded."""
+    from dsce.coding import conv_encode, count_errors, make_code, viterbi_decode
+    from test_coding_ml_host import flip_of
+    llr, bits = oracle_llr
+    n, nk, ns, nd, m = llr.shape
+    code = make_code(nd * m, rate, terminated=terminated, interleaver=7)
+    flat = llr.reshape(n, nk, ns, nd * m)
+    lam = np.where(bits[:, None, None].astype(bool), -flat, flat).reshape(-1, nd * m)
+    u = np.random.default_rng(17).integers(0, 2, (lam.shape[0], code.n_steps)).astype(np.uint8)
+    u[:, code.n_info:] = 0
+    zero, _ = count_errors(viterbi_decode(lam, code.src, terminated), terminated)
+    sent, _ = count_errors(viterbi_decode(lam * flip_of(u, code, conv_encode), code.src, terminated) ^ u, terminated)
+    assert zero.shape == (n * nk * ns,) and np.array_equal(sent, zero), np.flatnonzero(sent != zero)
+    assert (zero > 0).sum() >= 15
+    if terminated:
+        assert sent.reshape(n, nk, ns).sum(axis=0).tolist() == ORACLE_COUNTS[rate]["bit_err"]
+        assert (sent > 0).reshape(n, nk, ns).sum(axis=0).tolist() == ORACLE_COUNTS[rate]["frame_err"]
 
 
 @pytest.mark.parametrize("extra,word", [(["--checkpoint", "ck.json"], "--checkpoint"),

@@ -6,7 +6,8 @@ LLR methods, both CSI branches and installed scale tables; and against itself
 across batch geometries, SNR chunks, staging bounds and split calls.  Every
 comparison is exact: the counts are integers and the twin performs the fp64
 operations of include/dsce.h in the same order.  Host outputs sit between guard
-regions."""
+regions.  tests/test_gpu_coded_ml.py holds the checks against references other
+than the twin."""
 import ctypes as C
 
 import numpy as np
