@@ -172,6 +172,7 @@ using namespace dsce;
 
 struct dsce_ctx {
     int device = 0;
+    int lds_dev = 0;               // the device's hipDeviceAttributeMaxSharedMemoryPerBlock (Opts::lds_max's ceiling)
     hipStream_t stream = nullptr;
     std::string err;
     bool chan_set = false;
@@ -911,6 +912,7 @@ void trim_w_band(dsce_ctx* c, Scheme& s, DeviceTemps& tmp) {
     setup_w_extent(st, s.Wb, NP, s.W, s.w_elems, nsl, dlohi);
     DSCE_HIP_CHECK(hipMemcpyAsync(lohi.data(), dlohi, lohi.size() * sizeof(int), hipMemcpyDeviceToHost, st));
     DSCE_HIP_CHECK(hipStreamSynchronize(st));
+    DSCE_HIP_CHECK(hipGetLastError());
     HostBand nb = s.wband;
     nb.vals.clear();
     long long off = 0;
@@ -985,6 +987,8 @@ void build_wpair(dsce_ctx* c, Scheme& s) {
     // W's 3M planes, two k-steps per 16-byte lane load
     s.Wp3 = dalloc<double>(c, (size_t)nsl * 3 * s.wp_elems);
     setup_wpair(c->stream, s.Wb, NP, s.W, s.w_elems, s.Pb, wp, s.wp_elems, nsl, s.Wp3);
+    DSCE_HIP_CHECK(hipStreamSynchronize(c->stream));
+    DSCE_HIP_CHECK(hipGetLastError());
     free_alloc(c, wp);
     // fused MMSE stage: block-diagonal W (every block's columns are its own 24
     // rows, OFDM), row-local precoder, select-mode detection, NP = 16
@@ -1341,6 +1345,11 @@ void build_mic(dsce_ctx* c, Scheme& s, const SetupArgs& a, const double2* m, con
 void build_mmse(dsce_ctx* c, Scheme& s, double thr) {
     hipStream_t st = c->stream;
     const int N = s.N, LK = s.LK, NP = s.d.n_pilots, Nsym = s.d.n_tx_symbols, nsnr = c->nsnr;
+    // lds_max may have been lowered since dsce_add_scheme checked it
+    if (hp_tile_lds_bytes(NP) > (size_t)c->op.lds_max)
+        throw ApiError(DSCE_EINVAL, "n_pilots " + std::to_string(NP) + " needs " + std::to_string(hp_tile_lds_bytes(NP)) +
+                                        " bytes of LDS per workgroup; the limit (lds_max) is " +
+                                        std::to_string(c->op.lds_max));
     DeviceTemps tmp(c);
     if (s.W) {                     // rebuild (e.g. new SNR list): back to the structural band
         free_alloc(c, s.W);
@@ -1448,7 +1457,10 @@ void build_mmse(dsce_ctx* c, Scheme& s, double thr) {
     DSCE_HIP_CHECK(hipMemcpy(dR, s.R_est.data(), (size_t)nsnr * NP * NP * sizeof(double2), hipMemcpyHostToDevice));
     DSCE_HIP_CHECK(hipMemcpy(dR + (size_t)nsnr * NP * NP, s.R_noI.data(), (size_t)nsnr * NP * NP * sizeof(double2),
                              hipMemcpyHostToDevice));
-    setup_rinv(st, NP, 2 * nsnr, dR, dRi);
+    // k_rinv's 3 NP^2 working elements: in LDS while they fit (NP <= 36 under RINV_LDS_MAX), else in device memory
+    const bool rinv_in_lds = rinv_lds_bytes(NP) <= std::min<size_t>(RINV_LDS_MAX, (size_t)c->op.lds_max);
+    double2* rwork = rinv_in_lds ? nullptr : tmp.alloc<double2>((size_t)2 * nsnr * 3 * NP * NP);
+    setup_rinv(st, NP, 2 * nsnr, dR, dRi, rwork);
     // R_Dij packed, then W / W0 per SNR
     double2* rd = tmp.alloc<double2>((size_t)s.w_elems);
     Band Wb = s.Wb;
@@ -2299,6 +2311,8 @@ int dsce_create(int hip_device, dsce_ctx** out) {
         DSCE_HIP_CHECK(hipSetDevice(hip_device));
         DSCE_HIP_CHECK(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
         DSCE_HIP_CHECK(hipDeviceGetAttribute(&ctx->op.dev_cus, hipDeviceAttributeMultiprocessorCount, hip_device));
+        DSCE_HIP_CHECK(hipDeviceGetAttribute(&ctx->lds_dev, hipDeviceAttributeMaxSharedMemoryPerBlock, hip_device));
+        ctx->op.lds_max = ctx->lds_dev;
     } catch (const std::exception& e) {
         delete ctx;
         return DSCE_EHIP;
@@ -2512,6 +2526,17 @@ int dsce_set_snr(dsce_ctx* ctx, const double* pn_time, int32_t n_snr, int32_t n_
     return fanout(ctx, [&](dsce_ctx* c) { return set_snr_one(c, pn_time, n_snr, n_iter); });
 }
 
+// The kernels whose dynamic LDS grows with the pilot count (k_ls_hest and k_wcontract_valu: an [NP][64] tile;
+// k_rinv has a device-memory form, build_mmse) must fit the context's limit: checked here, on the host, so no
+// launch ever asks for more than the device gives.
+static void check_pilot_lds(const dsce_ctx* ctx, int n_pilots) {
+    const size_t need = hp_tile_lds_bytes(n_pilots);
+    if (need > (size_t)ctx->op.lds_max)
+        throw ApiError(DSCE_EINVAL, "n_pilots " + std::to_string(n_pilots) + " needs " + std::to_string(need) +
+                                        " bytes of LDS per workgroup (k_ls_hest, k_wcontract_valu); the limit is " +
+                                        std::to_string(ctx->op.lds_max));
+}
+
 static int add_scheme_one(dsce_ctx* ctx, const dsce_scheme_desc* d, int32_t* scheme_id) {
     TraceRange trace_range("dsce_add_scheme");
     API_BEGIN
@@ -2523,6 +2548,7 @@ static int add_scheme_one(dsce_ctx* ctx, const dsce_scheme_desc* d, int32_t* sch
     if (LK <= 0 || d->n_pilots <= 0 || d->n_pilots > DSCE_MAX_NP || d->n_data <= 0 ||
         d->n_tx_symbols != d->n_pilots + d->n_data)
         throw ApiError(DSCE_EINVAL, "inconsistent scheme dimensions");
+    check_pilot_lds(ctx, d->n_pilots);
     if (d->mod_order < 2 || d->mod_order > 256 || (d->mod_order & (d->mod_order - 1)) ||
         (1 << d->bits_per_symbol) != d->mod_order)
         throw ApiError(DSCE_EINVAL, "modulation order must be a power of two <= 256");
@@ -3733,7 +3759,7 @@ int dsce_fp64_mfma_peak(dsce_ctx* ctx, double* tflops) {
 // Kernel-selection options (Opts); the defaults are the measured-best path.
 #define DSCE_OPTIONS(X)                                                                                  \
     X(xcd) X(fuse_stage) X(pic_chain) X(pfuse) X(stage_split) X(noise_fuse) \
-    X(snr_chunk) X(jakes_rpw) X(wtrim) X(wcontract_valu) X(mmse_ic) X(jakes_win) X(txrx_fft) X(snr_base) X(jakes_mom) X(realise_win) X(tx_rows) X(mic_lr) X(pic_poly) X(jakes_grp2) X(export_stage_mb) X(snr_loop)
+    X(snr_chunk) X(jakes_rpw) X(wtrim) X(wcontract_valu) X(mmse_ic) X(jakes_win) X(txrx_fft) X(snr_base) X(jakes_mom) X(realise_win) X(tx_rows) X(mic_lr) X(pic_poly) X(jakes_grp2) X(export_stage_mb) X(snr_loop) X(lds_max)
 
 static int set_option_one(dsce_ctx* ctx, const char* name, int64_t value) {
     API_BEGIN
@@ -3760,6 +3786,9 @@ static int set_option_one(dsce_ctx* ctx, const char* name, int64_t value) {
         throw ApiError(DSCE_EINVAL, "snr_loop: 0 (a block per 64 units) | 1 (a block walks its realisations' SNR points) | "
                                     "-1 (by grid size)");
     if (n == "export_stage_mb" && value < 1) throw ApiError(DSCE_EINVAL, "export_stage_mb: >= 1 (MiB)");
+    if (n == "lds_max" && (value < 1024 || value > ctx->lds_dev))
+        throw ApiError(DSCE_EINVAL, "lds_max: 1024 .. " + std::to_string(ctx->lds_dev) + " bytes (the device's limit per "
+                                    "workgroup; it can only be lowered)");
     if (value < -1 || value > 1 << 20) throw ApiError(DSCE_EINVAL, "option value out of range");
     *slot = (int)value;
     API_END

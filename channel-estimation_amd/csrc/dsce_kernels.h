@@ -43,6 +43,9 @@ struct Opts {
                               // the device (launch_perfect_chain)
     int dev_cus = 0;          // not an option: the compute units of the context's device (dsce_create), read
                               // by snr_loop's rule
+    int lds_max = 0;          // dynamic LDS in bytes a launch of this context may ask for: the device's
+                              // hipDeviceAttributeMaxSharedMemoryPerBlock (dsce_create); dsce_set_option can only
+                              // lower it (read by dsce_add_scheme and dsce_build_mmse)
     int export_stage_mb = 1024; // dsce_export_stages: bound in MiB on the bulk trace arrays of one sub-batch
                               // (whole 64-realisation waves; one wave is the floor)
 };
@@ -460,7 +463,13 @@ void setup_mcoef(hipStream_t s, const SetupArgs& a, const int* g_start, int GL, 
 void setup_rhp(hipStream_t s, const SetupArgs& a, const double2* m, double2* rhp);
 void setup_gp(hipStream_t s, const SetupArgs& a, double2* gp /* N x Nsym */);
 void setup_rest_diag(hipStream_t s, const SetupArgs& a, const double2* gp, const int* q_start, int QL, double* diag);
-void setup_rinv(hipStream_t s, int NP, int nmat, const double2* R, double2* Rinv);
+// Dynamic LDS by pilot count, compared on the host with Opts::lds_max before any launch (dsce_add_scheme,
+// build_mmse): k_rinv's in-LDS form (used up to RINV_LDS_MAX, the device-memory form beyond), and the [NP][64]
+// LS-estimate tile of k_ls_hest and k_wcontract_valu
+static constexpr size_t RINV_LDS_MAX = 64 * 1024;
+size_t rinv_lds_bytes(int NP);
+inline size_t hp_tile_lds_bytes(int NP) { return (size_t)NP * 64 * sizeof(double2); }
+void setup_rinv(hipStream_t s, int NP, int nmat, const double2* R, double2* Rinv, double2* work);
 // H_hat operator of the structured MMSE IC: bv[sl][q][n][p] = sum_p' m[p'][q][n - d_q]
 // Rinv_sl[p'][p] for the nsl = 2 nsnr inverses; bs[sl][blk][q][p] = its sums over
 // the FFT windows [klo[blk], klo[blk] + win)

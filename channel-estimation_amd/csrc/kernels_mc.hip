@@ -4123,7 +4123,7 @@ unsigned launch_wcontract(hipStream_t s, const Opts& op, const SchemeK& sk, cons
         });
         return PATH_WPAIR3;
     }
-    hipLaunchKernelGGL(k_wcontract_valu, dim3(b.U / WAVE, mm.Wb.nblk), dim3(WAVE), sk.NP * WAVE * sizeof(double2), s,
+    hipLaunchKernelGGL(k_wcontract_valu, dim3(b.U / WAVE, mm.Wb.nblk), dim3(WAVE), hp_tile_lds_bytes(sk.NP), s,
                        mm.Wb, mm.W, mm.w_elems, var, mm.nsnr, b.snr0, sk.NP, b.R, b.U, b.hp, b.v, b.y, b.yest);
     return PATH_WCONTRACT_VALU;
 }
@@ -4364,7 +4364,7 @@ unsigned launch_stage(hipStream_t s, const Opts& op, const SchemeK& sk, const Mm
     hipLaunchKernelGGL(k_ls, dim3(b.U / WAVE), dim3(WAVE), 0, s, sk, st, b.xp, b.hp);
     const bool bulk = b.bulk();
     hipLaunchKernelGGL(bulk ? k_ls_hest_bulk : k_ls_hest, dim3(b.U / WAVE, rblk), dim3(WAVE),
-                       (size_t)sk.NP * WAVE * sizeof(double2), s, sk, st, mm.Wd, b.h, b.hp, b.e, b.e2);
+                       hp_tile_lds_bytes(sk.NP), s, sk, st, mm.Wd, b.h, b.hp, b.e, b.e2);
     hipLaunchKernelGGL(bulk ? k_detect_bulk : k_detect, dim3(b.U / WAVE, (sk.ND + DET_CHUNK - 1) / DET_CHUNK),
                        dim3(WAVE), 0, s, sk, st, b.sidx, b.e, b.e2, b.qe, b.qp, counters);
     if (!last)

@@ -161,9 +161,13 @@ void setup_rest_diag(hipStream_t s, const SetupArgs& a, const double2* gp, const
 }
 
 // pinv(R) for a Hermitian positive-definite NP x NP R: Gauss-Jordan with partial
-// pivoting in LDS, one workgroup per matrix (script:283-285, :302-304).
-__global__ void k_rinv(int NP, const double2* __restrict__ Rall, double2* __restrict__ Iall) {
-    extern __shared__ double2 Aug[];          // NP x 2NP, row-major
+// pivoting, one workgroup per matrix (script:283-285, :302-304).  The 3 NP^2
+// working elements sit in LDS (work null, NP <= 36) or, beyond RINV_LDS_MAX, in
+// the workgroup's slice of `work` in device memory: the same statements on the
+// same values, made visible between the steps by the same barriers.
+__global__ void k_rinv(int NP, const double2* __restrict__ Rall, double2* __restrict__ Iall, double2* work) {
+    extern __shared__ double2 rinv_lds[];
+    double2* Aug = work ? work + (size_t)blockIdx.x * 3 * NP * NP : rinv_lds;     // NP x 2NP, row-major
     __shared__ int piv;
     const double2* R = Rall + (size_t)blockIdx.x * NP * NP;
     double2* Ri = Iall + (size_t)blockIdx.x * NP * NP;
@@ -231,8 +235,12 @@ __global__ void k_rinv(int NP, const double2* __restrict__ Rall, double2* __rest
     }
 }
 
-void setup_rinv(hipStream_t s, int NP, int nmat, const double2* R, double2* Rinv) {
-    hipLaunchKernelGGL(k_rinv, dim3(nmat), dim3(256), (size_t)NP * 3 * NP * sizeof(double2), s, NP, R, Rinv);
+size_t rinv_lds_bytes(int NP) { return (size_t)NP * 3 * NP * sizeof(double2); }
+
+// work: null (the matrices in LDS; the caller has checked rinv_lds_bytes(NP) against RINV_LDS_MAX and the
+// device's limit) or nmat x 3 NP^2 elements of device memory
+void setup_rinv(hipStream_t s, int NP, int nmat, const double2* R, double2* Rinv, double2* work) {
+    hipLaunchKernelGGL(k_rinv, dim3(nmat), dim3(256), work ? 0 : rinv_lds_bytes(NP), s, NP, R, Rinv, work);
 }
 
 // The channel-estimate operator of the structured MMSE IC (k_mic_fft):

@@ -145,12 +145,32 @@ typedef struct {
     const double* pdp_norm;     /* n_taps, PowerDelayProfileNormalized (:129) */
 } dsce_channel_desc;
 
+/* The frame is caller data.  Accepted: any n_subcarriers, n_symbols >= 1 (LK is
+ * no multiple of anything: row blocks may be partial and may straddle symbols),
+ * any N (dsce_channel_desc), 1 <= n_pilots <= 64 (no multiple of 4 required),
+ * n_data >= 1, n_tx_symbols = n_pilots + n_data, pilot_pos and data_pos anywhere
+ * in 0..LK-1 (frame corners and edges included).  Outside that domain
+ * dsce_add_scheme returns DSCE_EINVAL ("inconsistent scheme dimensions",
+ * "pilot / data position out of range") and adds nothing.  The frame selects
+ * kernels, never results: the FFT forms need 24-row blocks on 24-sample windows,
+ * the polyphase form L = 24 or 48, the pair-tile contraction NP in {8, 16, 32},
+ * the fused stage the same, the structured MMSE IC NP = 16; every other frame
+ * runs the banded passes, k_wcontract_valu and k_ls_hest + k_detect + k_precode
+ * (tests/geometries.py).
+ * LDS: k_ls_hest and k_wcontract_valu keep an [n_pilots][64] complex tile in
+ * dynamic LDS (1024 n_pilots bytes: 64 KiB at 64 pilots).  dsce_add_scheme
+ * compares that on the host with the context's limit (option lds_max: the
+ * device's hipDeviceAttributeMaxSharedMemoryPerBlock unless lowered) and returns
+ * DSCE_EINVAL naming n_pilots and the limit when it does not fit, so no launch
+ * asks for more than the device gives.  dsce_build_mmse's inverse (k_rinv, 48
+ * n_pilots^2 bytes) works in LDS up to 64 KiB (n_pilots <= 36) and in device
+ * memory beyond, with the same arithmetic: every n_pilots up to 64 builds. */
 typedef struct {
-    int32_t n_subcarriers;      /* L                                          */
-    int32_t n_symbols;          /* K; LK = L*K columns of G and Q              */
+    int32_t n_subcarriers;      /* L >= 1                                      */
+    int32_t n_symbols;          /* K >= 1; LK = L*K columns of G and Q         */
     int32_t n_tx_symbols;       /* columns of P: NP + ND                       */
-    int32_t n_pilots;           /* NP                                          */
-    int32_t n_data;             /* ND                                          */
+    int32_t n_pilots;           /* NP, 1..64 (DSCE_EINVAL outside)             */
+    int32_t n_data;             /* ND >= 1                                     */
     int32_t mod_order;          /* M (power of two, 2..256; larger: DSCE_EINVAL) */
     int32_t bits_per_symbol;    /* log2(M); any of 1..8 (3- and 6-bit symbols   */
                                 /* straddle the BITS stream's words, ABI 8)     */
@@ -841,7 +861,10 @@ int dsce_jakes_info(dsce_ctx* ctx, int32_t* out6);
  *   stage 0: 1 = a block per 64 realisations and symbol walks the chunk's SNR
  *   points, the per-realisation prologue once, DSCE_PATH_SNR_LOOP; 0 = a block
  *   per 64 units; -1, the default: the loop where its grid still fills the
- *   device; same counts either way).
+ *   device; same counts either way), lds_max (bytes of dynamic LDS a launch of
+ *   the context may ask for; default and ceiling: the device's
+ *   hipDeviceAttributeMaxSharedMemoryPerBlock, floor 1024; read by
+ *   dsce_add_scheme and dsce_build_mmse, see dsce_scheme_desc).
  * Retired after r06 (no scheme or channel selected their other values;
  * DSCE_EINVAL): pic_net, mic_net (the DPP form of the chain kernels' 4-point
  * network; the matrix-core form is the only one), stage_rb (k_stage_fused runs 8

@@ -265,22 +265,22 @@ def _oracle_counts(S, name):
     return res
 
 
-def _check_counts(eng, res, what="", n=64):
+def _check_counts(eng, res, what="", n=64, seed=SEED):
     """The run's counters of realisations 0..n-1 against the oracle's res of the same range."""
-    cg = eng.run(SEED, 0, n)
+    cg = eng.run(seed, 0, n)
     assert cg.shape == res["err"].shape
     assert np.abs(cg - res["err"]).sum() <= 8 * res["borderline"].sum(), (what, eng.path_info(0), cg - res["err"])
     return eng.path_info(0)
 
 
-def _check_unit(S, eng, name, rep=3, yperf_rows=None):
+def _check_unit(S, eng, name, rep=3, yperf_rows=None, seed=SEED):
     """One unit (rep 3, both SNR points) per element through _check_trace
     (1e-10 for y and h, 1e-9 per stage); y_perf of the IC iterations on
     `yperf_rows` (the rows the path forms)."""
     tr = {}
-    harness.simulate(S, SEED, rep, 1, [name], trace=tr)
+    harness.simulate(S, seed, rep, 1, [name], trace=tr)
     for k in range(len(S.pn_time)):
-        g = eng.trace_unit(0, SEED, rep, k)
+        g = eng.trace_unit(0, seed, rep, k)
         u = tr["units"][k]
         ns = _check_trace(g, u, "%s %s snr %d" % (name, S.variant, k))
         assert ns == S.n_iter + 1
