@@ -3196,6 +3196,182 @@ int dsce_viterbi(dsce_ctx* ctx, const dsce_code_desc* code, int64_t n_slots, con
     API_END
 }
 
+// The checks of an LDPC description against n_slots slots and the context's LDS limit (dsce_run_ldpc, dsce_ldpc)
+static void check_ldpc(const dsce_ctx* ctx, const dsce_ldpc_desc* d, int64_t n_slots, const std::string& w) {
+    if (!d || !d->row_ptr || !d->col || !d->slot) throw ApiError(DSCE_EINVAL, w + ": null code, row_ptr, col or slot");
+    if (d->n_vars < 1) throw ApiError(DSCE_EINVAL, w + ": n_vars < 1");
+    if (d->n_checks < 1) throw ApiError(DSCE_EINVAL, w + ": n_checks < 1");
+    if (d->n_info < 1 || d->n_info > d->n_vars) throw ApiError(DSCE_EINVAL, w + ": n_info outside 1 .. n_vars");
+    if (d->max_iter < 1 || d->max_iter > DSCE_LDPC_MAX_ITER)
+        throw ApiError(DSCE_EINVAL, w + ": max_iter outside 1 .. DSCE_LDPC_MAX_ITER (100)");
+    if (!(std::isfinite(d->alpha) && d->alpha > 0.0 && d->alpha <= 1.0))
+        throw ApiError(DSCE_EINVAL, w + ": alpha must be finite with 0 < alpha <= 1");
+    if (d->early_stop != 0 && d->early_stop != 1) throw ApiError(DSCE_EINVAL, w + ": early_stop must be 0 or 1");
+    // the limit first: it bounds N and M, so the table walks below are short
+    const size_t need = ldpc_lds_bytes(d->n_vars, d->n_checks);
+    if (need > (size_t)ctx->op.lds_max)
+        throw ApiError(DSCE_EINVAL, w + ": a code of " + std::to_string(d->n_vars) + " variables and " +
+                                        std::to_string(d->n_checks) + " checks needs " + std::to_string(need) +
+                                        " bytes of LDS per workgroup (k_ldpc); the limit (lds_max) is " +
+                                        std::to_string(ctx->op.lds_max));
+    if (d->row_ptr[0] != 0) throw ApiError(DSCE_EINVAL, w + ": row_ptr[0] is not 0");
+    for (int c = 0; c < d->n_checks; ++c) {
+        const int64_t deg = (int64_t)d->row_ptr[c + 1] - d->row_ptr[c];
+        if (deg < 2 || deg > DSCE_LDPC_MAX_CHECK_DEGREE)
+            throw ApiError(DSCE_EINVAL, w + ": row_ptr gives check " + std::to_string(c) + " degree " +
+                                            std::to_string(deg) + " (2 .. DSCE_LDPC_MAX_CHECK_DEGREE = 32)");
+        for (int e = d->row_ptr[c]; e < d->row_ptr[c + 1]; ++e) {
+            if (d->col[e] < 0 || d->col[e] >= d->n_vars)
+                throw ApiError(DSCE_EINVAL, w + ": col entry outside [0, n_vars)");
+            if (e > d->row_ptr[c] && d->col[e] <= d->col[e - 1])
+                throw ApiError(DSCE_EINVAL, w + ": col of check " + std::to_string(c) + " is not strictly ascending");
+        }
+    }
+    for (int v = 0; v < d->n_vars; ++v)
+        if (d->slot[v] < -1 || (int64_t)d->slot[v] >= n_slots)
+            throw ApiError(DSCE_EINVAL, w + ": slot entry outside [-1, slots)");
+}
+
+// The device tables of a checked description: H by check as given, and by variable
+// (a variable's edges in ascending check order, check << 5 | position), uploaded once per call
+static LdpcCodeK upload_ldpc(dsce_ctx* ctx, DeviceTemps& tmp, const dsce_ldpc_desc* d) {
+    const int N = d->n_vars, M = d->n_checks;
+    const size_t E = (size_t)d->row_ptr[M];
+    std::vector<int> host((size_t)M + 1 + E + (size_t)N + 1 + E + (size_t)N);
+    int* row_ptr = host.data();
+    int* col = row_ptr + M + 1;
+    int* vptr = col + E;
+    int* vedge = vptr + N + 1;
+    int* slot = vedge + E;
+    std::copy(d->row_ptr, d->row_ptr + M + 1, row_ptr);
+    std::copy(d->col, d->col + E, col);
+    std::copy(d->slot, d->slot + N, slot);
+    std::fill(vptr, vptr + N + 1, 0);
+    for (size_t e = 0; e < E; ++e) ++vptr[col[e] + 1];
+    for (int v = 0; v < N; ++v) vptr[v + 1] += vptr[v];
+    std::vector<int> at(vptr, vptr + N);
+    for (int c = 0; c < M; ++c)
+        for (int e = row_ptr[c]; e < row_ptr[c + 1]; ++e) vedge[at[col[e]]++] = (c << 5) | (e - row_ptr[c]);
+    int* dev = tmp.alloc<int>(host.size());
+    DSCE_HIP_CHECK(hipMemcpyAsync(dev, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));      // `host` goes out of scope
+    LdpcCodeK k{};
+    k.row_ptr = dev;
+    k.col = dev + (col - row_ptr);
+    k.vptr = dev + (vptr - row_ptr);
+    k.vedge = dev + (vedge - row_ptr);
+    k.slot = dev + (slot - row_ptr);
+    k.N = N;
+    k.M = M;
+    k.n_info = d->n_info;
+    k.max_iter = d->max_iter;
+    k.early_stop = d->early_stop;
+    k.alpha = d->alpha;
+    return k;
+}
+
+// Coded bit and frame errors and iteration counts of a min-sum LDPC decoder
+// (DSCE_HAS_LDPC_RUN): dsce_run_coded's run (the same k_llr temporary, the same
+// sub-batches) with k_ldpc, one workgroup per codeword, in place of k_viterbi.
+int dsce_run_ldpc(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, uint64_t n_rep, uint32_t flags,
+                  const dsce_ldpc_desc* code, const dsce_ldpc_out* out) {
+    TraceRange trace_range("dsce run ldpc");
+    API_BEGIN
+    check_ctx(ctx);
+    Scheme& s = bulk_export_check(ctx, id, out, flags, DSCE_LLR_MAXLOG | DSCE_LLR_PERFECT, "dsce_run_ldpc");
+    const bool perfect = (flags & DSCE_LLR_PERFECT) != 0, maxlog = (flags & DSCE_LLR_MAXLOG) != 0;
+    const int ND = s.d.n_data, nsnr = ctx->nsnr, S = ctx->niter + 1, m = s.d.bits_per_symbol;
+    const size_t B = (size_t)ND * m;
+    check_ldpc(ctx, code, (int64_t)B, "dsce_run_ldpc");
+    ExportSink sink{"dsce_run_ldpc", 3, {out->bit_err, out->frame_err, out->iter_sum}, {0, 0, 0},
+                    {sizeof(int64_t), sizeof(int64_t), sizeof(int64_t)}, false};
+    const size_t ncell = (size_t)nsnr * S;
+    const bool any = out->bit_err || out->frame_err || out->iter_sum;
+    const int chunk = snr_chunk(ctx);
+    const size_t extra = (S * B * sizeof(double) * (size_t)nsnr + chunk - 1) / chunk;
+    const int rsub = bulk_sub_batch(ctx, s, perfect, extra);
+    std::vector<unsigned long long> host(3 * ncell);
+    DeviceTemps tmp(ctx);
+    LdpcK q{};
+    unsigned long long* acc = nullptr;
+    double* dllr = nullptr;
+    if (any) {
+        // no field requested: bulk_export refuses below, before anything is launched
+        acc = tmp.alloc<unsigned long long>(3 * ncell);
+        DSCE_HIP_CHECK(hipMemsetAsync(acc, 0, 3 * ncell * sizeof(unsigned long long), ctx->stream));
+        q.acc_bit = out->bit_err ? acc : nullptr;
+        q.acc_frame = out->frame_err ? acc + ncell : nullptr;
+        q.acc_iter = out->iter_sum ? acc + 2 * ncell : nullptr;
+        q.c = upload_ldpc(ctx, tmp, code);
+        if (n_rep > 0) dllr = tmp.alloc<double>((size_t)rsub * nsnr * S * B);
+    }
+    q.m = m;
+    q.B = (int)B;
+    q.S = S;
+    q.nsnr = nsnr;
+    bulk_export(ctx, s, id, seed, first_rep, n_rep, sink, [&](const Bulk& bk, int snr0) {
+        LlrK a = llr_args(ctx, s, bk, snr0, maxlog, perfect);
+        if (a.R > rsub || a.rvalid > a.R) throw ApiError(DSCE_EINVAL, "dsce_run_ldpc: LLR temporary too small");
+        a.row0 = 0;
+        a.out[2] = dllr;
+        {
+            Timed t(ctx, "k_llr");
+            launch_llr(ctx->stream, a, false);
+        }
+        q.llr = dllr;
+        q.sidx = ctx->buf.sidx;
+        q.R = a.R;
+        q.snr0 = snr0;
+        q.nchunk = a.U / a.R;
+        q.ncw = (long long)a.rvalid * q.nchunk * S;
+        Timed t(ctx, "k_ldpc");
+        launch_ldpc(ctx->stream, q);
+        DSCE_HIP_CHECK(hipGetLastError());
+    }, perfect, extra);
+    if (n_rep > 0 && any) {
+        DSCE_HIP_CHECK(hipMemcpyAsync(host.data(), acc, host.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                                      ctx->stream));
+        DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        for (size_t i = 0; out->bit_err && i < ncell; ++i) out->bit_err[i] += (int64_t)host[i];
+        for (size_t i = 0; out->frame_err && i < ncell; ++i) out->frame_err[i] += (int64_t)host[ncell + i];
+        for (size_t i = 0; out->iter_sum && i < ncell; ++i) out->iter_sum[i] += (int64_t)host[2 * ncell + i];
+    }
+    tmp.release_checked();
+    API_END
+}
+
+// The decoder of dsce_run_ldpc on the caller's lam: k_ldpc_probe, the same device
+// function with another load and store.  Needs only the context.
+int dsce_ldpc(dsce_ctx* ctx, const dsce_ldpc_desc* code, int64_t n_slots, const double* lam, int64_t n_cw,
+              uint8_t* bits_out, int32_t* iters_out) {
+    API_BEGIN
+    check_ctx(ctx);
+    if (n_slots < 0) throw ApiError(DSCE_EINVAL, "dsce_ldpc: n_slots < 0");
+    check_ldpc(ctx, code, n_slots, "dsce_ldpc");
+    if (n_cw < 0) throw ApiError(DSCE_EINVAL, "dsce_ldpc: n_cw < 0");
+    if (n_cw > 0 && (!lam || !bits_out)) throw ApiError(DSCE_EINVAL, "dsce_ldpc: null pointer");
+    if (n_cw > 0) {
+        const size_t N = (size_t)code->n_vars, nl = (size_t)n_cw * (size_t)n_slots;
+        DeviceTemps tmp(ctx);
+        const LdpcCodeK k = upload_ldpc(ctx, tmp, code);
+        double* dlam = tmp.alloc<double>(std::max<size_t>(nl, 1));
+        uint8_t* dbits = tmp.alloc<uint8_t>((size_t)n_cw * N);
+        int* dit = tmp.alloc<int>((size_t)n_cw);
+        if (nl) DSCE_HIP_CHECK(hipMemcpyAsync(dlam, lam, nl * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        {
+            Timed t(ctx, "k_ldpc");
+            launch_ldpc_probe(ctx->stream, k, n_cw, n_slots, dlam, dbits, dit);
+        }
+        DSCE_HIP_CHECK(hipGetLastError());
+        DSCE_HIP_CHECK(hipMemcpyAsync(bits_out, dbits, (size_t)n_cw * N, hipMemcpyDeviceToHost, ctx->stream));
+        if (iters_out)
+            DSCE_HIP_CHECK(hipMemcpyAsync(iters_out, dit, (size_t)n_cw * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        tmp.release_checked();
+        if (ctx->timing) collect_timing(ctx);
+    }
+    API_END
+}
+
 static int set_llr_scale_one(dsce_ctx* ctx, int32_t id, const double* g_est, const double* g_perf0) {
     API_BEGIN
     check_ctx(ctx);

@@ -438,6 +438,40 @@ void launch_viterbi(hipStream_t s, const CodedK& a);
 // the same decoder on lam [ncw][n_slots]: every decoded input to out [ncw][T] (k_viterbi_probe; dsce_viterbi)
 void launch_viterbi_probe(hipStream_t s, const int* src, int T, int terminated, long long ncw, long long n_slots,
                           const double* lam, uint8_t* out);
+// Normalised min-sum LDPC decoder of include/dsce.h (DSCE_HAS_LDPC_RUN; kernels_ldpc.hip): one workgroup per
+// codeword, flooding schedule.  H by check (row_ptr [M + 1], col [E], checked by the host) and by variable (vptr
+// [N + 1], vedge [E] = check << 5 | position in the check, a variable's edges in ascending check order); slot [N]
+// in [-1, slots).  Dynamic LDS per block: P [N] fp64, then per check m1, m2 (fp64), the sign mask and i1 | sg << 8
+// (24 M bytes), then two flag words: ldpc_lds_bytes, compared on the host with Opts::lds_max before any launch.
+struct LdpcCodeK {
+    const int* row_ptr;       // [M + 1]
+    const int* col;           // [E]
+    const int* vptr;          // [N + 1]
+    const int* vedge;         // [E]
+    const int* slot;          // [N]
+    int N, M, n_info, max_iter, early_stop;
+    double alpha;
+};
+inline size_t ldpc_lds_bytes(int N, int M) { return (size_t)N * 8 + (size_t)M * 24 + 8; }
+// k_ldpc after k_llr (dsce_run_ldpc): codeword = (realisation rl < rvalid, SNR point of the chunk, stage) as in
+// CodedK, ncw = rvalid nchunk S blocks; ell of slot j m + b is -lam, lam = k_llr's LLR negated where bit b of
+// sidx[j][rl] is 1.  The decoded ones among the first n_info variables go to acc_bit[snr][stage], 1 to acc_frame if
+// there are any, and the iterations performed to acc_iter, by integer atomics.
+struct LdpcK {
+    LdpcCodeK c;
+    long long ncw;
+    const double* llr;        // [R][nsnr][S][B]
+    const uint16_t* sidx;     // [ND][R] transmitted symbol indices
+    int m, B, S, R, nsnr, snr0, nchunk;
+    unsigned long long* acc_bit;     // [nsnr][S], or null
+    unsigned long long* acc_frame;   // [nsnr][S], or null
+    unsigned long long* acc_iter;    // [nsnr][S], or null
+};
+void launch_ldpc(hipStream_t s, const LdpcK& a);
+// the same decoder on lam [ncw][n_slots]: x to bits [ncw][N], the iterations performed to iters [ncw] (or null)
+// (k_ldpc_probe; dsce_ldpc)
+void launch_ldpc_probe(hipStream_t s, const LdpcCodeK& c, long long ncw, long long n_slots, const double* lam,
+                       uint8_t* bits, int* iters);
 // LLRs of n points x (pn: one value or one per point), out [n][m]
 void launch_llr_probe(hipStream_t s, const LlrTab& t, const double2* x, const double* pn, long long n_pn, long long n,
                       bool maxlog, double* out);

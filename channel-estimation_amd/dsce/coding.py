@@ -2,7 +2,9 @@
 rate-1/2, constraint-length-7 convolutional code (133, 171 octal), the code
 tables that carry interleaving and puncturing, and viterbi_decode, the NumPy
 twin of the engine's k_viterbi: the same fp64 operations in the same order, so
-its decisions equal the engine's to the bit.
+its decisions equal the engine's to the bit.  Below it the LDPC side
+(DSCE_HAS_LDPC_RUN): make_ldpc's systematic repeat-accumulate codes, their
+encoder, and ldpc_decode, the NumPy twin of k_ldpc.
 
 State s holds u_{t-1} in bit 0 .. u_{t-6} in bit 5; next state ns = ((s << 1) |
 u_t) & 63; the predecessors of ns are p_b = (ns >> 1) | (b << 5), b = 0, 1, with
@@ -172,3 +174,227 @@ def coded_counts(llr, sym, code):
     dec = viterbi_decode(lam.reshape(n * nk * S, nd * m), code.src, code.terminated)
     bit, frame = count_errors(dec, code.terminated)
     return dict(bit_err=bit.reshape(n, nk, S).sum(axis=0), frame_err=frame.reshape(n, nk, S).sum(axis=0))
+
+
+# ---- LDPC codes and the normalised min-sum decoder (include/dsce.h, DSCE_HAS_LDPC_RUN) ----
+
+LDPC_MAX_CHECK_DEGREE = 32
+LDPC_MAX_ITER = 100
+LDPC_RATES = {"1/2": (1, 2), "2/3": (2, 3), "3/4": (3, 4), "5/6": (5, 6)}
+
+LdpcCode = collections.namedtuple(
+    "LdpcCode", "row_ptr col slot n_vars n_checks n_info max_iter alpha early_stop n_slots rate four_cycles")
+LdpcCode.__doc__ = """An LDPC code for dsce_run_ldpc / dsce_ldpc: H by check in CSR form (row_ptr int32
+[n_checks + 1], col int32 [E], the variables of a check strictly ascending), slot int32
+[n_vars] (the slot that carries a variable, -1: punctured), variables 0 .. n_info - 1 the
+information bits, and the decoder's parameters.  four_cycles: the 4-cycles left in H
+(make_ldpc; None for a hand-made code)."""
+
+
+def ldpc_from_rows(rows, n_vars, n_info, slot=None, n_slots=None, max_iter=30, alpha=0.75, early_stop=True,
+                   rate=None, four_cycles=None):
+    """An LdpcCode from the variable lists of its checks (each sorted here)."""
+    rows = [sorted(int(v) for v in r) for r in rows]
+    row_ptr = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
+    col = np.array([v for r in rows for v in r], dtype=np.int32)
+    slot = np.arange(n_vars, dtype=np.int32) if slot is None else np.asarray(slot, dtype=np.int32)
+    if n_slots is None:
+        n_slots = int(slot.max()) + 1 if slot.size and slot.max() >= 0 else 0
+    return LdpcCode(row_ptr, col, slot, int(n_vars), len(rows), int(n_info), int(max_iter), float(alpha),
+                    bool(early_stop), int(n_slots), rate, four_cycles)
+
+
+def ldpc_four_cycles(code):
+    """The number of 4-cycles of H: sum over pairs of checks of C(common variables, 2)."""
+    H = np.zeros((code.n_checks, code.n_vars), dtype=np.float32)
+    H[np.repeat(np.arange(code.n_checks), np.diff(code.row_ptr)), code.col] = 1.0
+    G = np.rint(H @ H.T).astype(np.int64)
+    G = np.triu(G, 1)
+    return int((G * (G - 1) // 2).sum())
+
+
+def make_ldpc(n_slots, rate="1/2", seed=7, interleaver=7, max_iter=30, alpha=0.75, early_stop=True):
+    """A systematic repeat-accumulate code H = [H1 | H2] of N = n_slots variables for
+    `rate` ('1/2', '2/3', '3/4', '5/6'): K = n_slots * num // den information bits
+    (variables 0 .. K - 1) and M = N - K checks.  H2 is the M x M dual diagonal:
+    check i holds parity variables K + i and, for i > 0, K + i - 1.  H1 has column
+    weight 3 and row weights equal to within one: column after column, each of its
+    three rows is drawn from the rows of least weight, among them one that closes no
+    4-cycle with the columns placed so far or with H2 where there is one; four_cycles
+    reports those that remain.  Every draw comes from numpy.random.RandomState(seed),
+    a frozen stream.  Variable v travels in slot pi[v]: interleaver as for make_code
+    (an int seed, a permutation, or None for the identity)."""
+    if rate not in LDPC_RATES:
+        raise ValueError("rate must be one of %s" % sorted(LDPC_RATES))
+    num, den = LDPC_RATES[rate]
+    N = int(n_slots)
+    K = N * num // den
+    M = N - K
+    if K < 1 or M < 3:
+        raise ValueError("%d slots at rate %s give %d information bits and %d checks (at least 1 and 3)"
+                         % (N, rate, K, M))
+    if (3 * K + M - 1) // M + 2 > LDPC_MAX_CHECK_DEGREE:
+        raise ValueError("check degree above %d" % LDPC_MAX_CHECK_DEGREE)
+    rng = np.random.RandomState(int(seed))
+    weight = np.zeros(M, dtype=np.int64)
+    paired = np.zeros((M, M), dtype=bool)                 # rows that already share a column
+    idx = np.arange(M - 1)
+    paired[idx, idx + 1] = paired[idx + 1, idx] = True     # H2: column K + i joins checks i and i + 1
+    rows = [[] for _ in range(M)]
+    for j in range(K):
+        chosen = []
+        for _ in range(3):
+            free = np.ones(M, dtype=bool)
+            free[chosen] = False
+            cand = np.flatnonzero(free & (weight == weight[free].min()))
+            cand = cand[rng.permutation(cand.size)]
+            clean = cand[~paired[np.ix_(cand, chosen)].any(axis=1)] if chosen else cand
+            chosen.append(int(clean[0] if clean.size else cand[0]))
+            weight[chosen[-1]] += 1
+        for a in chosen:
+            rows[a].append(j)
+            for b in chosen:
+                if a != b:
+                    paired[a, b] = True
+    for i in range(M):
+        rows[i] += [K + i - 1, K + i] if i else [K]
+    if interleaver is None:
+        pi = np.arange(N)
+    elif isinstance(interleaver, (int, np.integer)):
+        pi = np.random.RandomState(int(interleaver)).permutation(N)
+    else:
+        pi = np.asarray(interleaver, dtype=np.int64).reshape(-1)
+        if pi.size != N or not np.array_equal(np.sort(pi), np.arange(N)):
+            raise ValueError("interleaver must be a permutation of range(n_slots)")
+    code = ldpc_from_rows(rows, N, K, slot=pi, n_slots=N, max_iter=max_iter, alpha=alpha, early_stop=early_stop,
+                          rate=rate)
+    return code._replace(four_cycles=ldpc_four_cycles(code))
+
+
+def ldpc_encode(u, code):
+    """The codewords [..][n_vars] (uint8) of the information words u [..][n_info] under a
+    make_ldpc code: the parity bits are the prefix XOR of H1 u, p_i = p_{i-1} ^ (H1 u)_i."""
+    u = np.asarray(u).astype(np.uint8) & 1
+    K, M = code.n_info, code.n_checks
+    if u.shape[-1] != K or code.n_vars != K + M:
+        raise ValueError("u must be [..][n_info] of a systematic code with n_vars = n_info + n_checks")
+    chk = np.repeat(np.arange(M), np.diff(code.row_ptr))
+    info = code.col < K
+    s = np.zeros(u.shape[:-1] + (M,), dtype=np.uint8)
+    np.bitwise_xor.at(s, (Ellipsis, chk[info]), u[..., code.col[info]])
+    return np.concatenate([u, np.bitwise_xor.accumulate(s, axis=-1)], axis=-1)
+
+
+def ldpc_lam(cw, code, amplitude=1.0):
+    """The noiseless decoder input of the codewords cw [..][n_vars]: lam [..][n_slots] =
+    +amplitude where the slot carries a 1, -amplitude for a 0, 0 in unused slots."""
+    cw = np.asarray(cw)
+    lam = np.zeros(cw.shape[:-1] + (code.n_slots,))
+    use = code.slot >= 0
+    lam[..., code.slot[use]] = amplitude * (2.0 * cw[..., use].astype(np.float64) - 1.0)
+    return lam
+
+
+def ldpc_syndrome(x, code):
+    """H x [..][n_checks] (uint8) of the words x [..][n_vars]."""
+    x = np.asarray(x).astype(np.uint8) & 1
+    return np.bitwise_xor.reduceat(x[..., code.col], code.row_ptr[:-1], axis=-1)
+
+
+def ldpc_decode(lam, code, _mutate=None):
+    """Normalised min-sum decoding of lam [n_cw][n_slots] (or [n_slots]; positive = the
+    bit is 1) under `code`: (x uint8 [n_cw][n_vars], it int32 [n_cw]), the decided bits
+    of the last iteration performed and the number of iterations.  The twin of k_ldpc,
+    in fp64 and in the order of include/dsce.h: ell_v = -lam[slot[v]] (0.0 for -1), P =
+    ell, R = 0; per iteration and check, over the edge positions p in order, q_p = P_v -
+    R_p, a_p = |q_p|, s_p = q_p < 0, m1 / i1 the minimum and the lowest position
+    attaining it, m2 the minimum of the others, sg the XOR of the s_p, R'_p = +-(alpha
+    * (p == i1 ? m2 : m1)), negative where sg ^ s_p; per variable P' = ((ell + R'_e1) +
+    R'_e2) + .. over its edges in ascending check order; x = P' < 0; with early_stop a
+    codeword stops once H x = 0.  _mutate is for the tests only: a deliberately wrong
+    decoder ('sign', 'no_exclude', 'alpha_late')."""
+    lam = np.asarray(lam, dtype=np.float64)
+    single = lam.ndim == 1
+    lam = np.ascontiguousarray(lam.reshape(-1, lam.shape[-1]))
+    n, N, M = lam.shape[0], code.n_vars, code.n_checks
+    row_ptr = np.asarray(code.row_ptr, dtype=np.int64)
+    col = np.asarray(code.col, dtype=np.int64)
+    slot = np.asarray(code.slot, dtype=np.int64)
+    alpha = float(code.alpha)
+    deg = np.diff(row_ptr)
+    E = col.size
+    chk = np.repeat(np.arange(M), deg)
+    pos = np.arange(E) - row_ptr[chk]
+    by_var = np.argsort(col, kind="stable")                 # a variable's edges in ascending check order
+    vdeg = np.bincount(col, minlength=N)
+    vptr = np.concatenate([[0], np.cumsum(vdeg)])
+    ell = np.zeros((n, N))
+    use = slot >= 0
+    ell[:, use] = -lam[:, slot[use]]
+    odd = (deg[chk] & 1).astype(bool)
+    P = ell.copy()
+    R = np.zeros((n, E))
+    x = np.zeros((n, N), dtype=np.uint8)
+    its = np.zeros(n, dtype=np.int32)
+    act = np.arange(n)
+    with np.errstate(invalid="ignore"):
+        for _ in range(int(code.max_iter)):
+            if act.size == 0:
+                break
+            Pa, Ra = P[act], R[act]
+            na = act.size
+            m1 = np.full((na, M), np.inf)
+            m2 = np.full((na, M), np.inf)
+            i1 = np.zeros((na, M), dtype=np.int64)
+            sg = np.zeros((na, M), dtype=bool)
+            sgn = np.zeros((na, E), dtype=bool)
+            for p in range(int(deg.max())):
+                cs = np.flatnonzero(deg > p)
+                e = row_ptr[cs] + p
+                q = Pa[:, col[e]] - Ra[:, e]
+                a = np.abs(q)
+                s = q < 0
+                sgn[:, e] = s
+                c1, c2 = m1[:, cs], m2[:, cs]
+                lt1 = a < c1
+                lt2 = ~lt1 & (a < c2)
+                m2[:, cs] = np.where(lt1, c1, np.where(lt2, a, c2))
+                m1[:, cs] = np.where(lt1, a, c1)
+                i1[:, cs] = np.where(lt1, p, i1[:, cs])
+                sg[:, cs] ^= s
+            mu = np.where(pos[None, :] == i1[:, chk], m2[:, chk], m1[:, chk])
+            if _mutate == "no_exclude":
+                mu = m1[:, chk]
+            r = mu if _mutate == "alpha_late" else alpha * mu
+            neg = sg[:, chk] ^ sgn
+            if _mutate == "sign":
+                neg = neg ^ odd[None, :]
+            Rn = np.where(neg, -r, r)
+            acc = ell[act].copy()
+            for k in range(int(vdeg.max()) if E else 0):
+                vs = np.flatnonzero(vdeg > k)
+                acc[:, vs] = acc[:, vs] + Rn[:, by_var[vptr[vs] + k]]
+            if _mutate == "alpha_late":
+                acc = alpha * acc
+            xa = (acc < 0).astype(np.uint8)
+            P[act], R[act], x[act] = acc, Rn, xa
+            its[act] += 1
+            if code.early_stop:
+                act = act[ldpc_syndrome(xa, code).any(axis=1)]
+    return (x[0], its[0]) if single else (x, its)
+
+
+def ldpc_counts(llr, sym, code):
+    """The definition of dsce_run_ldpc on exported arrays: llr [n][n_snr][S][ND][m]
+    (export_llr) and sym [n][ND] (export) -> dict(bit_err, frame_err, iter_sum), int64
+    [n_snr][S].  lam as in coded_counts; the decided information bits of the all-zero
+    codeword and the iterations performed are counted."""
+    llr = np.asarray(llr, dtype=np.float64)
+    n, nk, S, nd, m = llr.shape
+    t = ((np.asarray(sym)[..., None] >> np.arange(m)) & 1).astype(bool).reshape(n, 1, 1, nd * m)
+    flat = llr.reshape(n, nk, S, nd * m)
+    lam = np.where(t, -flat, flat)
+    x, it = ldpc_decode(lam.reshape(n * nk * S, nd * m), code)
+    bit = x[:, :code.n_info].astype(np.int64).sum(axis=1)
+    return dict(bit_err=bit.reshape(n, nk, S).sum(axis=0), frame_err=(bit > 0).astype(np.int64).reshape(n, nk, S).sum(axis=0),
+                iter_sum=it.astype(np.int64).reshape(n, nk, S).sum(axis=0))

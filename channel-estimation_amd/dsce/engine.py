@@ -31,6 +31,7 @@ EXPORTED = [
     "dsce_run_calib", "dsce_set_llr_scale", "dsce_get_llr_scale",
     "dsce_set_llr_scale_perf", "dsce_get_llr_scale_perf",
     "dsce_run_coded", "dsce_viterbi",
+    "dsce_run_ldpc", "dsce_ldpc",
 ]
 
 ABI_VERSION = 10
@@ -126,6 +127,17 @@ class CodedOut(C.Structure):
     _fields_ = [("bit_err", C.POINTER(C.c_int64)), ("frame_err", C.POINTER(C.c_int64))]
 
 
+class LdpcDesc(C.Structure):
+    _fields_ = [("n_vars", C.c_int32), ("n_checks", C.c_int32), ("row_ptr", C.POINTER(C.c_int32)),
+                ("col", C.POINTER(C.c_int32)), ("slot", C.POINTER(C.c_int32)), ("n_info", C.c_int32),
+                ("max_iter", C.c_int32), ("alpha", C.c_double), ("early_stop", C.c_int32)]
+
+
+class LdpcOut(C.Structure):
+    _fields_ = [("bit_err", C.POINTER(C.c_int64)), ("frame_err", C.POINTER(C.c_int64)),
+                ("iter_sum", C.POINTER(C.c_int64))]
+
+
 class TxDesc(C.Structure):
     _fields_ = [("kind", C.c_int32), ("n_subcarriers", C.c_int32), ("n_symbols", C.c_int32),
                 ("n_samples", C.c_int32), ("fft_size", C.c_int32), ("intermediate_bin", C.c_int32),
@@ -205,6 +217,10 @@ def load_library(path=None):
     lib.dsce_run_coded.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
                                    C.POINTER(CodeDesc), C.POINTER(CodedOut)]
     lib.dsce_viterbi.argtypes = [vp, C.POINTER(CodeDesc), C.c_int64, dp, C.c_int64, C.POINTER(C.c_uint8)]
+    lib.dsce_run_ldpc.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                  C.POINTER(LdpcDesc), C.POINTER(LdpcOut)]
+    lib.dsce_ldpc.argtypes = [vp, C.POINTER(LdpcDesc), C.c_int64, dp, C.c_int64, C.POINTER(C.c_uint8),
+                              C.POINTER(C.c_int32)]
     for name in EXPORTED:
         fn = getattr(lib, name)
         if name != "dsce_last_error":
@@ -760,6 +776,72 @@ class Engine:
         self._chk(self.lib.dsce_run_coded(self.h, int(sid), int(seed), int(first_rep), int(n_rep),
                                           self._llr_flag(method) | self._branch_flag(branch), C.byref(desc),
                                           C.byref(o)), "dsce_run_coded")
+        return out
+
+    # -- coded BER from a normalised min-sum LDPC decoder (DSCE_HAS_LDPC_RUN) ---------
+    @staticmethod
+    def _ldpc_desc(code):
+        """(LdpcDesc, the int32 arrays it points to) of a dsce.coding.LdpcCode"""
+        keep = tuple(np.ascontiguousarray(np.asarray(a).reshape(-1), dtype=np.int32)
+                     for a in (code.row_ptr, code.col, code.slot))
+        if keep[0].size != int(code.n_checks) + 1 or keep[2].size != int(code.n_vars):
+            raise ValueError("row_ptr must be [n_checks + 1] and slot [n_vars]")
+        if keep[0].size and keep[1].size != keep[0][-1]:
+            raise ValueError("col must have row_ptr[n_checks] entries")
+        ptr = [a.ctypes.data_as(C.POINTER(C.c_int32)) for a in keep]
+        return LdpcDesc(int(code.n_vars), int(code.n_checks), ptr[0], ptr[1], ptr[2], int(code.n_info),
+                        int(code.max_iter), float(code.alpha), int(code.early_stop)), keep
+
+    def ldpc(self, lam, code):
+        """The engine's min-sum decoder on caller-supplied lam [n_cw][n_slots] (or
+        [n_slots]; positive = the bit is 1) under `code` (dsce.coding.make_ldpc):
+        (x uint8 [n_cw][n_vars], it int32 [n_cw]), the decided bits and the
+        iterations performed (dsce_ldpc), equal to the bit to
+        dsce.coding.ldpc_decode.  Needs only the context."""
+        lam = np.asarray(lam, dtype=np.float64)
+        single = lam.ndim == 1
+        lam = np.ascontiguousarray(lam.reshape(-1, lam.shape[-1]))
+        desc, keep = self._ldpc_desc(code)
+        x = np.zeros((lam.shape[0], int(code.n_vars)), dtype=np.uint8)
+        it = np.zeros(lam.shape[0], dtype=np.int32)
+        self._chk(self.lib.dsce_ldpc(self.h, C.byref(desc), lam.shape[1], _dptr(lam), lam.shape[0],
+                                     x.ctypes.data_as(C.POINTER(C.c_uint8)), it.ctypes.data_as(C.POINTER(C.c_int32))),
+                  "dsce_ldpc")
+        return (x[0], it[0]) if single else (x, it)
+
+    def ldpc_shapes(self, sid):
+        """Shapes of dsce_run_ldpc's arrays for scheme sid."""
+        d = self.scheme_dims(sid)
+        return {f: (d.n_snr, d.n_iter + 1) for f in ("bit_err", "frame_err", "iter_sum")}
+
+    def run_ldpc(self, sid, seed, first_rep, n_rep, code, method="exact", out=None, branch="mmse"):
+        """Decoded-error counts of the LDPC code `code` (dsce.coding.make_ldpc(ND m,
+        rate)) over the LLRs that export_llr would return for realisations
+        [first_rep, first_rep + n_rep) of scheme sid, one codeword per realisation,
+        SNR point and stage, decoded on the GPU by normalised min-sum
+        (dsce_run_ldpc): dict of int64 arrays bit_err, frame_err and iter_sum
+        [n_snr][S].  The all-zero codeword is simulated under the BITS stream as
+        the scrambler, which is exact for this decoder (include/dsce.h).  The
+        counts are ADDED into the arrays of `out` (a dict with any of the keys,
+        C-contiguous int64; only the given ones are computed) and `out` is
+        returned; without it all are computed from zero.  BER = bit_err / (n_rep
+        code.n_info), FER = frame_err / n_rep, mean iterations = iter_sum / n_rep.
+        branch 'perfect' (DSCE_LLR_PERFECT): the LLRs of the perfect-CSI branch."""
+        shapes = self.ldpc_shapes(sid)
+        if out is None:
+            out = {f: np.zeros(shp, dtype=np.int64) for f, shp in shapes.items()}
+        o = LdpcOut()
+        for f, a in out.items():
+            if f not in shapes:
+                raise ValueError("unknown ldpc output %r (of %s)" % (f, list(shapes)))
+            if not (isinstance(a, np.ndarray) and a.dtype == np.int64 and a.flags.c_contiguous
+                    and a.shape == shapes[f]):
+                raise ValueError("%s must be a C-contiguous int64 array of shape %s" % (f, shapes[f]))
+            setattr(o, f, a.ctypes.data_as(C.POINTER(C.c_int64)))
+        desc, keep = self._ldpc_desc(code)
+        self._chk(self.lib.dsce_run_ldpc(self.h, int(sid), int(seed), int(first_rep), int(n_rep),
+                                         self._llr_flag(method) | self._branch_flag(branch), C.byref(desc),
+                                         C.byref(o)), "dsce_run_ldpc")
         return out
 
     # -- engine state ------------------------------------------------------------

@@ -78,6 +78,17 @@ def main(argv=None):
                          "--calibrate it runs after the scale tables are installed")
     ap.add_argument("--coded-interleaver", type=int, default=7, metavar="SEED",
                     help="with --coded: the interleaver is numpy.random.RandomState(SEED).permutation(ND m)")
+    ap.add_argument("--ldpc", choices=("1/2", "2/3", "3/4", "5/6"), default=None, metavar="RATE",
+                    help="also the LDPC-coded bit and frame error rate and the mean decoder iterations per scheme, "
+                         "SNR point and IC stage: a systematic repeat-accumulate code of RATE over the ND m slots "
+                         "(dsce.coding.make_ldpc), one codeword per realisation, decoded on the GPU by normalised "
+                         "min-sum with early stop from the demapper's LLRs (dsce_run_ldpc; exact LLRs, or --rate's "
+                         "method), MMSE and perfect-CSI branch.  Runs after --calibrate's tables and after --coded")
+    ap.add_argument("--ldpc-iters", type=int, default=30, metavar="N", help="with --ldpc: the iteration cap (1 .. 100)")
+    ap.add_argument("--ldpc-alpha", type=float, default=0.75, metavar="A",
+                    help="with --ldpc: the min-sum normalisation, 0 < A <= 1")
+    ap.add_argument("--ldpc-seed", type=int, default=7, metavar="S",
+                    help="with --ldpc: the code is drawn from numpy.random.RandomState(S)")
     a = ap.parse_args(argv)
     if (a.resume or a.stop_after is not None) and not a.checkpoint:
         raise SystemExit("--resume / --stop-after need --checkpoint")
@@ -99,6 +110,18 @@ def main(argv=None):
                          (a.config == "doubly_flat", "--config doubly_flat (its own simulator)")):
             if on:
                 raise SystemExit("--coded cannot be combined with " + what)
+    if a.ldpc:
+        # like the coded pass: one plain sweep of the rank's realisations after the counters
+        for on, what in ((a.checkpoint, "--checkpoint (the LDPC counts are not checkpointed)"),
+                         (a.shard == "snr", "--shard snr (the LDPC pass runs every SNR point of the engine)"),
+                         (a.devices, "--devices (dsce_run_ldpc is member 0's on a multi-device context)"),
+                         (a.config == "doubly_flat", "--config doubly_flat (its own simulator)")):
+            if on:
+                raise SystemExit("--ldpc cannot be combined with " + what)
+        if not 1 <= a.ldpc_iters <= 100:
+            raise SystemExit("--ldpc-iters must be 1 .. 100")
+        if not 0.0 < a.ldpc_alpha <= 1.0:
+            raise SystemExit("--ldpc-alpha must be in (0, 1]")
 
     from dsce import results
     from dsce.configs import build_setup
@@ -161,6 +184,9 @@ def main(argv=None):
     # --coded: [scheme][branch: mmse, perfect][field: bit_err, frame_err][snr][stage]
     coded = np.zeros((len(names), 2, 2, nsnr, nst), dtype=np.int64)
     codes, coded_s = [], 0.0
+    # --ldpc: [scheme][branch: mmse, perfect][field: bit_err, frame_err, iter_sum][snr][stage]
+    ldpc = np.zeros((len(names), 2, 3, nsnr, nst), dtype=np.int64)
+    ldpc_codes, ldpc_s = [], 0.0
     eng = None
     setup_s, t0 = 0.0, time.perf_counter()
     ck_path = None
@@ -261,6 +287,20 @@ def main(argv=None):
                     eng.run_coded(i, a.seed, first + at, min(step, mine - at), codes[i], a.rate or "exact", out,
                                   branch=branch)
         coded_s = time.perf_counter() - t1
+    if a.ldpc:
+        # one dsce_run_ldpc pass per scheme and branch over the same realisations, after --coded
+        from dsce.coding import make_ldpc
+        t1 = time.perf_counter()
+        for i, s in enumerate(names):
+            sc = S.schemes[s]
+            ldpc_codes.append(make_ldpc(int(sc.n_data) * int(sc.bits_per_symbol), a.ldpc, seed=a.ldpc_seed,
+                                        max_iter=a.ldpc_iters, alpha=a.ldpc_alpha))
+            for b, branch in enumerate(("mmse", "perfect") if mine else ()):
+                out = {"bit_err": ldpc[i, b, 0], "frame_err": ldpc[i, b, 1], "iter_sum": ldpc[i, b, 2]}
+                for at in range(0, mine, step):
+                    eng.run_ldpc(i, a.seed, first + at, min(step, mine - at), ldpc_codes[i], a.rate or "exact", out,
+                                 branch=branch)
+        ldpc_s = time.perf_counter() - t1
     if eng is not None:
         eng.close()
     complete = done >= mine
@@ -282,7 +322,7 @@ def main(argv=None):
             dist.destroy_process_group()
         return 0
     # "seconds" is the counter loop's: the rate pass is timed on its own
-    extra = {"setup_s": setup_s, "seconds": prior_s + time.perf_counter() - t0 - rate_s - coded_s, "ranks": world,
+    extra = {"setup_s": setup_s, "seconds": prior_s + time.perf_counter() - t0 - rate_s - coded_s - ldpc_s, "ranks": world,
              "shard": a.shard}
     if a.rate:
         extra["bicm_rate_seconds"] = rate_s
@@ -304,6 +344,8 @@ def main(argv=None):
             loss_pi = allreduce_counts(loss_pi, dev)
         if a.coded:
             coded = allreduce_counts(coded, dev)
+        if a.ldpc:
+            ldpc = allreduce_counts(ldpc, dev)
         if a.calibrate:
             closs_e = allreduce_counts(closs_e, dev)
             closs_p = allreduce_counts(closs_p, dev)
@@ -366,6 +408,20 @@ def main(argv=None):
             for b, branch in enumerate(("mmse", "perfect_ic")):
                 extra["coded"][s][branch] = {"ber": (coded[i, b, 0] / (float(reps) * k)).tolist(),
                                              "fer": (coded[i, b, 1] / float(reps)).tolist()}
+    if a.ldpc:
+        # BER = bit_err / (reps info_bits), FER = frame_err / reps, mean_iter = iter_sum / reps (include/dsce.h)
+        extra["ldpc_seconds"] = ldpc_s
+        extra["ldpc"] = {}
+        for i, s in enumerate(names):
+            c = ldpc_codes[i]
+            extra["ldpc"][s] = {"rate": a.ldpc, "info_bits": int(c.n_info), "n_checks": int(c.n_checks),
+                                "max_iter": int(c.max_iter), "alpha": float(c.alpha), "seed": int(a.ldpc_seed),
+                                "four_cycles": int(c.four_cycles), "method": a.rate or "exact",
+                                "calibrated": bool(a.calibrate)}
+            for b, branch in enumerate(("mmse", "perfect_ic")):
+                extra["ldpc"][s][branch] = {"ber": (ldpc[i, b, 0] / (float(reps) * c.n_info)).tolist(),
+                                            "fer": (ldpc[i, b, 1] / float(reps)).tolist(),
+                                            "mean_iter": (ldpc[i, b, 2] / float(reps)).tolist()}
     extra["realisations_per_s"] = reps / extra["seconds"]
     res = results.make(S, names, counts, bits, reps, a.seed, extra=extra)
     if rank != 0:
@@ -399,6 +455,14 @@ def main(argv=None):
                               "coded_fer_ic_mmse": r["mmse"]["fer"][k][-1],
                               "coded_ber_ic_perfect": r["perfect_ic"]["ber"][k][-1]}
                           for s, r in extra["coded"].items()}))
+    if a.ldpc:
+        print(json.dumps({s: {"snr_db": float(S.snr_db[k]), "rate": r["rate"], "info_bits": r["info_bits"],
+                              "ldpc_ber_ic_mmse": r["mmse"]["ber"][k][-1],
+                              "ldpc_ber_onetap_mmse": r["mmse"]["ber"][k][0],
+                              "ldpc_fer_ic_mmse": r["mmse"]["fer"][k][-1],
+                              "ldpc_mean_iter_ic_mmse": r["mmse"]["mean_iter"][k][-1],
+                              "ldpc_ber_ic_perfect": r["perfect_ic"]["ber"][k][-1]}
+                          for s, r in extra["ldpc"].items()}))
     if distributed:
         dist.destroy_process_group()
     return 0

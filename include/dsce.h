@@ -46,6 +46,9 @@
  *   dsce_run_coded        <- no counterpart in the script: the bit and frame errors of a
  *                            K = 7 Viterbi decoder fed with those LLRs, per SNR point and stage
  *   dsce_viterbi          <- the same decoder on the caller's own decoder input
+ *   dsce_run_ldpc         <- no counterpart in the script: the bit and frame errors and the
+ *                            iterations of a normalised min-sum LDPC decoder on those LLRs
+ *   dsce_ldpc             <- the same decoder on the caller's own decoder input
  *
  * Conventions
  *  - Return 0 on success, a negative DSCE_E* code on failure; the message is
@@ -103,6 +106,8 @@
  * every stage) with dsce_set_llr_scale_perf and dsce_get_llr_scale_perf.
  * DSCE_HAS_CODED_RUN (still ABI 10) announces dsce_run_coded and dsce_viterbi:
  * the coded bit and frame errors of a K = 7 Viterbi decoder on the device.
+ * DSCE_HAS_LDPC_RUN (still ABI 10) announces dsce_run_ldpc and dsce_ldpc: the
+ * same counts from a normalised min-sum decoder of a caller-given LDPC code.
  */
 #ifndef DSCE_H
 #define DSCE_H
@@ -769,8 +774,8 @@ int dsce_get_llr_scale_perf(dsce_ctx* ctx, int32_t scheme_id, double* g_perf, in
  *  zeros), else K = T; bit_err = the number of decoded u_t = 1 for t < K;
  *  frame_err = 1 if bit_err is non-zero.  One codeword per realisation, SNR point
  *  and stage; BER = bit_err / (n_rep K), FER = frame_err / n_rep.
- *  Not built: other codes, both branches in one call, sharding over a
- *  multi-device handle. */
+ *  Not built: both branches in one call, sharding over a multi-device handle.
+ *  Another code: the LDPC section below. */
 #define DSCE_HAS_CODED_RUN 1
 #define DSCE_CODE_MAX_STEPS 8192   /* the decision words of a codeword (8 bytes per step) stay within 64 KiB of LDS */
 typedef struct {
@@ -814,6 +819,126 @@ int dsce_run_coded(dsce_ctx* ctx, int32_t scheme_id, uint64_t seed, uint64_t fir
  * does nothing. */
 int dsce_viterbi(dsce_ctx* ctx, const dsce_code_desc* code, int64_t n_slots, const double* lam, int64_t n_cw,
                  uint8_t* info_out);
+
+/* ---- coded BER from a normalised min-sum LDPC decoder (DSCE_HAS_LDPC_RUN;
+ *      additive, ABI 10) ---------------------------------------------------- */
+/* Definitions.
+ *  Code: any binary parity-check matrix H with M = n_checks rows and N = n_vars
+ *  columns, given by check in CSR form: the variables of check c are
+ *  col[row_ptr[c] .. row_ptr[c+1] - 1], strictly ascending (no variable twice, and
+ *  the position p of a variable in its check is fixed by that order).  A check
+ *  joins 2 .. DSCE_LDPC_MAX_CHECK_DEGREE = 32 variables: a check of one variable
+ *  would send +-inf and then form inf - inf, and 32 lets the signs of a check be
+ *  one 32-bit mask.  A variable may be in any number of checks, none included.
+ *  Slots: those of dsce_run_coded, slot j m + b = bit b of data symbol j.  slot[v]
+ *  is the slot that carries variable v, or -1 for a punctured or shortened
+ *  variable, which contributes 0.0.  Interleaving is nothing but this table, and a
+ *  slot may carry more than one variable.  Variables 0 .. n_info - 1 are the
+ *  information bits: the host orders the variables so (dsce/coding.py make_ldpc
+ *  builds systematic repeat-accumulate codes of rates 1/2, 2/3, 3/4 and 5/6; the
+ *  engine does not know about rates or constructions).
+ *  Decoder input: lam as for dsce_run_coded, lam[i] = t_i ? -LLR_i : LLR_i,
+ *  positive means "the descrambled bit is 1".
+ *  Decoder (fp64, exactly this order, no clipping, no renormalisation, no fused
+ *  multiply-add; dsce/coding.py ldpc_decode is the bit-identical NumPy twin):
+ *   1. ell_v = slot[v] < 0 ? 0.0 : -lam[slot[v]].  Inside the decoder POSITIVE MEANS
+ *      "THE BIT IS 0", the opposite of lam: with that convention the sign of a
+ *      check's message is the plain XOR of the other signs; with lam's own
+ *      convention it would depend on the parity of the check's degree.  The
+ *      negation is exact.
+ *   2. P_v = ell_v, and R_{c,p} = 0.0 for every edge (p = position in check c).
+ *   3. One iteration, flooding schedule (every check reads the P and R of the
+ *      previous iteration):
+ *      check c with variables v_0 .. v_{d-1}:
+ *        q_p = P_{v_p} - R_{c,p},  a_p = |q_p|,  s_p = (q_p < 0);
+ *        m1 = min_p a_p, i1 = the lowest p attaining it, m2 = min over p != i1 of
+ *        a_p, sg = XOR of all s_p;
+ *        mu_p = (p == i1 ? m2 : m1),  r = alpha * mu_p (one rounded product);
+ *        R'_{c,p} = (sg ^ s_p) ? -r : r;
+ *      variable v, its edges e1, e2, .. in ascending check order:
+ *        P'_v = ((ell_v + R'_{e1}) + R'_{e2}) + ...;
+ *      x_v = (P'_v < 0);
+ *      it += 1; if early_stop is set and every check's XOR of x is 0, stop.
+ *   4. After max_iter iterations at the latest the output is x of the last
+ *      iteration performed, and it.
+ *  A kernel may keep (m1, m2, i1, sg, the mask of s_p) per check instead of R per
+ *  edge: R_{c,p} recomputed from that record is the same bits.
+ *  Counts: bit_err = the number of x_v = 1 for v < n_info; frame_err = 1 if
+ *  bit_err is non-zero; iter_sum = it.  One codeword per realisation, SNR point and
+ *  stage; BER = bit_err / (n_rep n_info), FER = frame_err / n_rep, mean iterations
+ *  = iter_sum / n_rep.
+ *  Why the all-zero codeword is exact.  As for dsce_run_coded nothing is encoded:
+ *  the all-zero codeword is simulated under the scrambler t.  Sending codeword c
+ *  instead multiplies ell_v by (1 - 2 c_v).  Both updates are sign-symmetric: if
+ *  every P_v and R_{c,p} of one iteration is multiplied by (1 - 2 c_v), then |q_p|
+ *  is unchanged, s_p becomes s_p ^ c_{v_p} wherever q_p != 0, sg is unchanged since
+ *  the c of a check XOR to 0, so R'_{c,p} is multiplied by (1 - 2 c_{v_p}) and P'_v
+ *  by (1 - 2 c_v), exactly (negation commutes with rounding).  By induction x
+ *  becomes x ^ c, the syndrome of x is unchanged and so is it.  The decided word
+ *  XOR the sent word is the all-zero decode, iteration count included.
+ *  The caveat: an exactly zero P_v (or q_p) is decided as 0 whatever c_v is, so in
+ *  the all-zero simulation it counts as correct although a transmitted 1 there
+ *  would have been an error.  That matters only for a punctured variable that
+ *  never receives information; for LLRs of a continuous channel it has negligible
+ *  probability, like the Viterbi ties above.  lam is expected to be finite.
+ *  Kernel: one workgroup per codeword; P (8 N bytes) and the check records (24 M
+ *  bytes) live in dynamic LDS, 8 N + 24 M + 8 bytes in all (51 KiB for N = 2560 at
+ *  rate 1/2, 30 KiB at rate 5/6).  The calls compare that on the host with the
+ *  context's limit (option lds_max) and return DSCE_EINVAL naming the bytes and the
+ *  limit when the code does not fit, before anything is launched.
+ *  Not built: several small codewords per workgroup, a layered schedule, offset
+ *  min-sum or sum-product, a device-memory fallback for codes beyond the LDS
+ *  limit, a MEX command, both branches in one call, sharding over a multi-device
+ *  handle. */
+#define DSCE_HAS_LDPC_RUN 1
+#define DSCE_LDPC_MAX_CHECK_DEGREE 32
+#define DSCE_LDPC_MAX_ITER 100
+typedef struct {
+    int32_t n_vars;         /* N >= 1 */
+    int32_t n_checks;       /* M >= 1 */
+    const int32_t* row_ptr; /* [n_checks + 1], row_ptr[0] = 0, each check 2 .. 32 entries */
+    const int32_t* col;     /* [row_ptr[n_checks]] variables of each check, strictly ascending */
+    const int32_t* slot;    /* [n_vars] slot of variable v, or -1 (punctured / shortened) */
+    int32_t n_info;         /* 1 .. n_vars: variables 0 .. n_info - 1 are counted */
+    int32_t max_iter;       /* 1 .. DSCE_LDPC_MAX_ITER */
+    double alpha;           /* finite, 0 < alpha <= 1 */
+    int32_t early_stop;     /* 0 | 1: stop once x satisfies every check */
+} dsce_ldpc_desc;
+
+typedef struct {            /* each optional */
+    int64_t* bit_err;       /* [n_snr][1 + n_iter] */
+    int64_t* frame_err;     /* [n_snr][1 + n_iter] */
+    int64_t* iter_sum;      /* [n_snr][1 + n_iter] */
+} dsce_ldpc_out;
+
+/* dsce_run_coded with the decoder above: ADDS the counts into the caller's int64
+ * host arrays.  The same run (realisations, batches, SNR chunks, the
+ * export_stage_mb cut with the k_llr temporary counted, padding realisations that
+ * count nowhere, n_rep = 0 adding nothing, no change to the error counters, the
+ * MSE sums or dsce_path_info), the same "k_llr" temporary holding the bits of
+ * dsce_export_llr for the same flags, installed scale tables included; then
+ * "k_ldpc" (its name under dsce_enable_timing) decodes one codeword per workgroup
+ * and adds its counts to device int64 accumulators with integer atomics: any order
+ * gives the same counts.  flags: 0 | DSCE_LLR_MAXLOG | DSCE_LLR_PERFECT.
+ * DSCE_EINVAL, with a message naming the offender and nothing written: any other
+ * flag bit; a null code, row_ptr, col or slot; n_vars, n_checks, n_info, max_iter,
+ * alpha or early_stop outside the bounds above; row_ptr[0] != 0; a check of degree
+ * below 2 or above 32 (so a row_ptr that does not increase); a col entry outside
+ * [0, n_vars) or not strictly ascending within its check; a slot entry outside
+ * [-1, ND m); a code that does not fit lds_max; a null out and no field requested.
+ * DSCE_ESTATE as for dsce_run_coded.  On a multi-device handle the call is member
+ * 0's. */
+int dsce_run_ldpc(dsce_ctx* ctx, int32_t scheme_id, uint64_t seed, uint64_t first_rep, uint64_t n_rep,
+                  uint32_t flags, const dsce_ldpc_desc* code, const dsce_ldpc_out* out);
+
+/* The same decoder (the device function of dsce_run_ldpc, with another load and
+ * store) for caller-supplied lam [n_cw][n_slots]: nothing is descrambled, and any
+ * codeword is decoded.  bits_out [n_cw][n_vars]: x of every variable, 0 / 1;
+ * iters_out [n_cw] (optional): the iterations performed.  Needs only a context.
+ * DSCE_EINVAL for the code errors above (slot entries in [-1, n_slots)), n_slots <
+ * 0, n_cw < 0 and a null lam or bits_out with n_cw > 0; n_cw = 0 does nothing. */
+int dsce_ldpc(dsce_ctx* ctx, const dsce_ldpc_desc* code, int64_t n_slots, const double* lam, int64_t n_cw,
+              uint8_t* bits_out, int32_t* iters_out);
 
 /* ---- engine state ------------------------------------------------------- */
 int dsce_scheme_dims(dsce_ctx* ctx, int32_t scheme_id, dsce_dims* dims);
@@ -864,7 +989,8 @@ int dsce_jakes_info(dsce_ctx* ctx, int32_t* out6);
  *   device; same counts either way), lds_max (bytes of dynamic LDS a launch of
  *   the context may ask for; default and ceiling: the device's
  *   hipDeviceAttributeMaxSharedMemoryPerBlock, floor 1024; read by
- *   dsce_add_scheme and dsce_build_mmse, see dsce_scheme_desc).
+ *   dsce_add_scheme and dsce_build_mmse, see dsce_scheme_desc, and by
+ *   dsce_run_ldpc and dsce_ldpc).
  * Retired after r06 (no scheme or channel selected their other values;
  * DSCE_EINVAL): pic_net, mic_net (the DPP form of the chain kernels' 4-point
  * network; the matrix-core form is the only one), stage_rb (k_stage_fused runs 8

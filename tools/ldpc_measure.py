@@ -1,0 +1,134 @@
+"""Measures dsce_run_ldpc (k_ldpc) on one GPU at the C2 export shape of DESIGN.md
+section 7k (default config, OFDM, 7 SNR points, n_iter 4, 8192 realisations at
+batch 8192), rates 1/2 and 3/4, 30 iterations, alpha 0.75, exact LLRs:
+
+  * kernel time (dsce_kernel_time) of k_ldpc with early stop on and off and of
+    k_llr beside it, same process, after a warm-up call, `repeats` calls, the
+    best and every value;
+  * codewords per second, the mean iterations per SNR point and stage, and the
+    time per codeword and iteration they imply;
+  * k_viterbi at the same shape from the same run, as the yardstick in the tree;
+  * dynamic LDS per block, and VGPRs, SGPRs, static LDS and scratch of the
+    instance of k_ldpc that runs (hipcc --cuda-device-only -S, the Makefile's
+    flags).
+
+    python tools/ldpc_measure.py --out profiles/ldpc_measure.json
+"""
+import argparse
+import json
+import os
+import re
+import subprocess
+import sys
+import tempfile
+import time
+
+import torch          # before the engine's library: one HIP runtime for both
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "channel-estimation_amd")
+sys.path[:0] = [PKG]
+
+SEED = 0x5EED0002
+FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form=1"]
+
+
+def kernel_resources(vpt):
+    """.amdhsa_* of k_ldpc<vpt>"""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    with tempfile.TemporaryDirectory() as d:
+        out = os.path.join(d, "k.s")
+        subprocess.run([hipcc] + FLAGS + ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(PKG, "csrc"),
+                                          "--cuda-device-only", "-S", os.path.join(PKG, "csrc", "kernels_ldpc.hip"),
+                                          "-o", out], check=True, capture_output=True)
+        txt = open(out).read()
+    m = re.search(r"\.amdhsa_kernel (\S*6k_ldpcILi%dE\S*)\n(.*?)\.end_amdhsa_kernel" % vpt, txt, re.S)
+    f = dict(re.findall(r"\.amdhsa_(\w+) (\S+)", m.group(2)))
+    return {"kernel": m.group(1), "vgprs": int(f["next_free_vgpr"]), "sgprs": int(f["next_free_sgpr"]),
+            "lds_static_bytes": int(f["group_segment_fixed_size"]), "scratch_bytes": int(f["private_segment_fixed_size"])}
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--reps", type=int, default=8192)
+    ap.add_argument("--batch", type=int, default=8192)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--alpha", type=float, default=0.75)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args(argv)
+
+    from dsce.coding import make_code, make_ldpc
+    from dsce.configs import build_setup
+    from dsce.engine import build_engine, gpu_tx
+    S = build_setup("default", schemes=("ofdm",), tx=gpu_tx(0))
+    eng = build_engine(S, batch=a.batch)
+    sc = S.schemes["ofdm"]
+    B = int(sc.n_data) * int(sc.bits_per_symbol)
+    nk, ns = len(S.snr_db), int(S.n_iter) + 1
+    ncw = a.reps * nk * ns
+    res = {"config": "default", "scheme": "ofdm", "n_snr": nk, "snr_db": [float(x) for x in S.snr_db],
+           "n_iter": int(S.n_iter), "slots": B, "reps": a.reps, "batch": a.batch,
+           "device": torch.cuda.get_device_name(0), "repeats": a.repeats, "method": "exact", "codewords": ncw,
+           "max_iter": a.iters, "alpha": a.alpha, "lds_max": eng.get_option("lds_max"), "rates": {}}
+
+    def timed(fn, names):
+        eng.enable_timing(True)
+        before = {k: eng.kernel_time(k) for k in names}
+        w0 = time.perf_counter()
+        out = fn()
+        w = time.perf_counter() - w0
+        after = {k: eng.kernel_time(k) for k in before}
+        eng.enable_timing(False)
+        return {k: after[k][1] - before[k][1] for k in before}, w, out
+
+    for rate in ("1/2", "3/4"):
+        r = {}
+        for early in (1, 0):
+            code = make_ldpc(B, rate, max_iter=a.iters, alpha=a.alpha, early_stop=bool(early))
+            run = lambda: eng.run_ldpc(0, SEED, 0, a.reps, code)
+            run()                                            # warm-up (buffers, clocks, code objects)
+            kd, kl, wall = [], [], []
+            for _ in range(a.repeats):
+                ms, w, out = timed(run, ("k_ldpc", "k_llr"))
+                kd.append(ms["k_ldpc"])
+                kl.append(ms["k_llr"])
+                wall.append(w)
+            best = min(kd)
+            iters = float(out["iter_sum"].sum())
+            r["early_stop" if early else "all_iterations"] = {
+                "k_ldpc_ms": kd, "k_ldpc_ms_best": best, "k_llr_ms": kl, "wall_s": wall,
+                "codewords_per_s": ncw / (best * 1e-3),
+                "mean_iter": (out["iter_sum"] / float(a.reps)).tolist(),
+                "mean_iter_all": iters / ncw,
+                # each codeword also spends one check phase more than its iterations where it stops early
+                "us_per_codeword_iteration": best * 1e3 / iters,
+                "ber": (out["bit_err"] / (a.reps * float(code.n_info))).tolist(),
+                "fer": (out["frame_err"] / float(a.reps)).tolist()}
+        nt = min(1024, (max(code.n_vars, code.n_checks) + 63) // 64 * 64)
+        vpt = -(-code.n_vars // nt)
+        vpt = next(v for v in (1, 2, 4, 8, 16, 0) if v == 0 or vpt <= v)
+        r.update({"info_bits": code.n_info, "n_checks": code.n_checks, "edges": int(code.col.size),
+                  "four_cycles": code.four_cycles, "threads_per_block": nt, "variables_per_thread": vpt,
+                  "lds_dynamic_bytes_per_block": 8 * code.n_vars + 24 * code.n_checks + 8})
+        try:
+            r["k_ldpc_resources"] = kernel_resources(vpt)
+        except Exception as e:                               # no compiler here: the run is still measured
+            r["k_ldpc_resources"] = {"error": str(e)[:200]}
+        conv = make_code(B, rate, interleaver=7)
+        runv = lambda: eng.run_coded(0, SEED, 0, a.reps, conv)
+        runv()
+        kv = [timed(runv, ("k_viterbi",))[0]["k_viterbi"] for _ in range(a.repeats)]
+        r["k_viterbi_ms"] = kv
+        r["k_ldpc_over_k_viterbi"] = {k: r[k]["k_ldpc_ms_best"] / min(kv) for k in ("early_stop", "all_iterations")}
+        res["rates"][rate] = r
+    eng.close()
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+    print(json.dumps(res))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
