@@ -2114,6 +2114,74 @@ void bulk_export(dsce_ctx* ctx, Scheme& s, int32_t id, uint64_t seed, uint64_t f
     tmp.release_checked();
 }
 
+// The accumulators of a call that sums on the device and adds into the caller's
+// arrays once (dsce_run_soft, dsce_run_calib: double; dsce_run_coded,
+// dsce_run_ldpc: unsigned long long counts into the caller's int64): the caller's
+// arrays and their lengths, in the kernel's order.  alloc(): one zeroed device
+// block from the call's DeviceTemps for the requested fields, dev(i) field i's
+// part of it or null; nothing when no field is requested (bulk_export then refuses
+// before any launch).  add_back() after the run: one copy, the stream wait, the
+// sums added.  Declare it before the call's DeviceTemps, and so before
+// bulk_export's temporaries: the block is freed with the former, after its stream
+// wait, and `host`, which a queued copy fills, outlives both holders' waits.
+template <class T, class Out = T>
+struct CallAcc {
+    struct Field {
+        Out* dst;
+        size_t n;
+    };
+    std::vector<Field> f;
+    std::vector<T> host;
+    T* block = nullptr;
+    CallAcc(std::initializer_list<Field> fields) : f(fields) {}
+
+    // where field i starts among the requested ones
+    size_t off(size_t i) const {
+        size_t o = 0;
+        for (size_t k = 0; k < i; ++k) o += f[k].dst ? f[k].n : 0;
+        return o;
+    }
+    void alloc(dsce_ctx* ctx, DeviceTemps& tmp) {
+        host.resize(off(f.size()));
+        if (host.empty()) return;
+        block = tmp.alloc<T>(host.size());
+        DSCE_HIP_CHECK(hipMemsetAsync(block, 0, host.size() * sizeof(T), ctx->stream));
+    }
+    T* dev(size_t i) const { return block && f[i].dst ? block + off(i) : nullptr; }
+    // The fields carry no per-realisation data (per_rep 0): the sink checks that
+    // one is requested and moves nothing.
+    ExportSink sink(const char* what) const {
+        ExportSink k{what, (int)f.size(), {}, {}, {}, false};
+        for (size_t i = 0; i < f.size(); ++i) {
+            k.dst[i] = f[i].dst;
+            k.esz[i] = sizeof(Out);
+        }
+        return k;
+    }
+    void add_back(dsce_ctx* ctx) {
+        if (!block) return;
+        DSCE_HIP_CHECK(hipMemcpyAsync(host.data(), block, host.size() * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+        DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        for (size_t i = 0; i < f.size(); ++i)
+            for (size_t k = 0; f[i].dst && k < f[i].n; ++k) f[i].dst[k] += (Out)host[off(i) + k];
+    }
+};
+
+// The stages dsce_run_soft / dsce_run_calib sum, of the S of the estimated branch
+// (field <stem>_est) followed by stage 0 of the perfect-CSI one (<stem>_perf0):
+// [st_lo, st_lo + nst).  DSCE_LLR_PERFECT makes the former the perfect branch, so
+// the latter is refused with it.
+struct StageWindow {
+    int st_lo, nst;
+};
+StageWindow stage_window(const char* what, const std::string& stem, bool perfect, const void* est, const void* perf0,
+                         int S) {
+    if (perfect && perf0)
+        throw ApiError(DSCE_EINVAL, std::string(what) + ": " + stem + "_perf0 with DSCE_LLR_PERFECT (it is stage 0 of " +
+                                        stem + "_est)");
+    return {est ? 0 : S, (est ? S : 0) + (perf0 ? 1 : 0)};
+}
+
 // Algorithmic work per realisation of one timed kernel group of a scheme
 // (dsce_kernel_work).  Flops: 8 per complex multiply-accumulate, 2 per real
 // FMA, 5 n log2 n per n-point DFT (the FFT convention), transcendental
@@ -2969,14 +3037,12 @@ int dsce_export_llr(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep
 
 // BICM information loss (DSCE_HAS_SOFT_RUN): dsce_export_llr's run with
 // k_llr_info + k_llr_info_sum after each SNR chunk in place of k_llr: the LLRs are
-// turned into loss_b with the batch's own sidx and summed into device
-// accumulators that live for the call (declared before bulk_export's temporaries,
-// so they outlive its stream wait), then added into the caller's arrays once.
-// The sink's two fields carry no per-realisation data (per_rep 0): it checks that
-// one is requested and moves nothing.  b.h and b.sidx are the realisation's own at
-// flush time on every path of run_batch: the TX kernels write sidx once per batch,
-// k_txrx_fft / the diag(D) band pass write h (the former with the first chunk
-// only), and every later kernel takes both as const.
+// turned into loss_b with the batch's own sidx and summed into the call's device
+// accumulators (CallAcc), then added into the caller's arrays once.  b.h and
+// b.sidx are the realisation's own at flush time on every path of run_batch: the
+// TX kernels write sidx once per batch, k_txrx_fft / the diag(D) band pass write h
+// (the former with the first chunk only), and every later kernel takes both as
+// const.
 int dsce_run_soft(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, uint64_t n_rep, uint32_t flags,
                   const dsce_soft_out* out) {
     TraceRange trace_range("dsce run soft");
@@ -2984,43 +3050,31 @@ int dsce_run_soft(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, 
     check_ctx(ctx);
     Scheme& s = bulk_export_check(ctx, id, out, flags, DSCE_LLR_MAXLOG | DSCE_LLR_PERFECT, "dsce_run_soft");
     const bool perfect = (flags & DSCE_LLR_PERFECT) != 0;
-    if (perfect && out->loss_perf0)
-        throw ApiError(DSCE_EINVAL, "dsce_run_soft: loss_perf0 with DSCE_LLR_PERFECT (it is stage 0 of loss_est)");
     const int ND = s.d.n_data, nsnr = ctx->nsnr, S = ctx->niter + 1;
-    ExportSink sink{"dsce_run_soft", 2, {out->loss_est, out->loss_perf0}, {0, 0}, {sizeof(double), sizeof(double)}, false};
-    const size_t n_est = out->loss_est ? (size_t)nsnr * S * 2 : 0, n_perf = out->loss_perf0 ? (size_t)nsnr * 2 : 0;
+    const StageWindow win = stage_window("dsce_run_soft", "loss", perfect, out->loss_est, out->loss_perf0, S);
+    CallAcc<double> acc{{out->loss_est, (size_t)nsnr * S * 2}, {out->loss_perf0, (size_t)nsnr * 2}};
+    ExportSink sink = acc.sink("dsce_run_soft");
     LlrInfoK q{};
-    q.st_lo = out->loss_est ? 0 : S;
-    q.nst = (out->loss_est ? S : 0) + (out->loss_perf0 ? 1 : 0);
-    std::vector<double> host(n_est + n_perf);
+    q.st_lo = win.st_lo;
+    q.nst = win.nst;
+    const int rmax = (ctx->batch + 63) / 64 * 64;
     DeviceTemps tmp(ctx);
-    if (q.nst > 0) {
-        // no field requested: bulk_export refuses below, before anything is launched
-        double* acc = tmp.alloc<double>(n_est + n_perf);
-        DSCE_HIP_CHECK(hipMemsetAsync(acc, 0, (n_est + n_perf) * sizeof(double), ctx->stream));
-        q.acc_est = out->loss_est ? acc : nullptr;
-        q.acc_perf = out->loss_perf0 ? acc + n_est : nullptr;
-        const int rmax = (ctx->batch + 63) / 64 * 64;
-        q.part = tmp.alloc<double>(llr_info_parts(ND, rmax, snr_chunk(ctx), q.nst));
-    }
+    acc.alloc(ctx, tmp);
+    q.acc_est = acc.dev(0);
+    q.acc_perf = acc.dev(1);
+    if (acc.block) q.part = tmp.alloc<double>(llr_info_parts(ND, rmax, snr_chunk(ctx), q.nst));
     bulk_export(ctx, s, id, seed, first_rep, n_rep, sink, [&](const Bulk& bk, int snr0) {
         LlrK& a = q.k;
         a = llr_args(ctx, s, bk, snr0, (flags & DSCE_LLR_MAXLOG) != 0, perfect);
         q.scale_perf = s.g_perf0;
         q.sidx = ctx->buf.sidx;
         q.considered = s.k.considered;
-        if (a.R > (ctx->batch + 63) / 64 * 64 || a.U / a.R > snr_chunk(ctx))
+        if (a.R > rmax || a.U / a.R > snr_chunk(ctx))
             throw ApiError(DSCE_EINVAL, "dsce_run_soft: partial sums too small");
         Timed t(ctx, "k_llr_info");
         launch_llr_info(ctx->stream, q);
     }, perfect);
-    if (n_rep > 0 && !host.empty()) {
-        DSCE_HIP_CHECK(hipMemcpyAsync(host.data(), q.acc_est ? q.acc_est : q.acc_perf, host.size() * sizeof(double),
-                                      hipMemcpyDeviceToHost, ctx->stream));
-        DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        for (size_t i = 0; i < n_est; ++i) out->loss_est[i] += host[i];
-        for (size_t i = 0; i < n_perf; ++i) out->loss_perf0[i] += host[n_est + i];
-    }
+    if (n_rep > 0) acc.add_back(ctx);
     tmp.release_checked();
     API_END
 }
@@ -3028,9 +3082,7 @@ int dsce_run_soft(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, 
 // Demapper noise ratio (DSCE_HAS_LLR_SCALE): dsce_run_soft's run with k_llr_calib
 // after each SNR chunk: per (SNR point, stage, data symbol) the sum over the
 // realisations of c |x_est - s_t|^2 / pn_eff against the unscaled AWGN pn_eff
-// (installed tables are not read).  The device accumulators live for the call
-// (declared before bulk_export's temporaries, so they outlive its stream wait)
-// and are added into the caller's arrays once.
+// (installed tables are not read), into the call's device accumulators (CallAcc).
 int dsce_run_calib(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, uint64_t n_rep, uint32_t flags,
                    const dsce_calib_out* out) {
     TraceRange trace_range("dsce run calib");
@@ -3038,40 +3090,116 @@ int dsce_run_calib(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep,
     check_ctx(ctx);
     Scheme& s = bulk_export_check(ctx, id, out, flags, DSCE_LLR_PERFECT, "dsce_run_calib");
     const bool perfect = (flags & DSCE_LLR_PERFECT) != 0;
-    if (perfect && out->ratio_perf0)
-        throw ApiError(DSCE_EINVAL, "dsce_run_calib: ratio_perf0 with DSCE_LLR_PERFECT (it is stage 0 of ratio_est)");
     const int ND = s.d.n_data, nsnr = ctx->nsnr, S = ctx->niter + 1;
-    ExportSink sink{"dsce_run_calib", 2, {out->ratio_est, out->ratio_perf0}, {0, 0}, {sizeof(double), sizeof(double)},
-                    false};
-    const size_t n_est = out->ratio_est ? (size_t)nsnr * S * ND : 0, n_perf = out->ratio_perf0 ? (size_t)nsnr * ND : 0;
+    const StageWindow win = stage_window("dsce_run_calib", "ratio", perfect, out->ratio_est, out->ratio_perf0, S);
+    CallAcc<double> acc{{out->ratio_est, (size_t)nsnr * S * ND}, {out->ratio_perf0, (size_t)nsnr * ND}};
+    ExportSink sink = acc.sink("dsce_run_calib");
     LlrCalibK q{};
-    q.st_lo = out->ratio_est ? 0 : S;
-    q.nst = (out->ratio_est ? S : 0) + (out->ratio_perf0 ? 1 : 0);
-    std::vector<double> host(n_est + n_perf);
+    q.st_lo = win.st_lo;
+    q.nst = win.nst;
     DeviceTemps tmp(ctx);
-    if (q.nst > 0) {
-        // no field requested: bulk_export refuses below, before anything is launched
-        double* acc = tmp.alloc<double>(n_est + n_perf);
-        DSCE_HIP_CHECK(hipMemsetAsync(acc, 0, (n_est + n_perf) * sizeof(double), ctx->stream));
-        q.acc_est = out->ratio_est ? acc : nullptr;
-        q.acc_perf = out->ratio_perf0 ? acc + n_est : nullptr;
-    }
+    acc.alloc(ctx, tmp);
+    q.acc_est = acc.dev(0);
+    q.acc_perf = acc.dev(1);
     bulk_export(ctx, s, id, seed, first_rep, n_rep, sink, [&](const Bulk& bk, int snr0) {
         q.k = llr_args(ctx, s, bk, snr0, false, perfect);
         q.sidx = ctx->buf.sidx;
         Timed t(ctx, "k_llr_calib");
         launch_llr_calib(ctx->stream, q);
     }, perfect);
-    if (n_rep > 0 && !host.empty()) {
-        DSCE_HIP_CHECK(hipMemcpyAsync(host.data(), q.acc_est ? q.acc_est : q.acc_perf, host.size() * sizeof(double),
-                                      hipMemcpyDeviceToHost, ctx->stream));
-        DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        for (size_t i = 0; i < n_est; ++i) out->ratio_est[i] += host[i];
-        for (size_t i = 0; i < n_perf; ++i) out->ratio_perf0[i] += host[n_est + i];
-    }
+    if (n_rep > 0) acc.add_back(ctx);
     tmp.release_checked();
     API_END
 }
+
+// (templates need C++ linkage)
+extern "C++" {
+
+using CountAcc = CallAcc<unsigned long long, int64_t>;
+
+// The run behind dsce_run_coded and dsce_run_ldpc, after the entry point's own
+// checks: dsce_run_soft's run with a decoder in place of the sum.  After each SNR
+// chunk k_llr, unmodified and in its fp64 instance with llr only, writes the
+// chunk's LLRs into a device temporary in the export layout,
+// [rsub][n_snr][S][ND m] with row0 = 0 (k_llr indexes by the absolute SNR index,
+// so the temporary has every SNR row; its bytes per unit count towards
+// export_stage_mb): the bits of dsce_export_llr.  decode() then launches the
+// decoder under its Timed name on the codewords `cw` describes (CodewordK); its
+// counts go to acc, whose fields 0 and 1 are cw's acc_bit and acc_frame.
+// upload(tmp) puts the code tables on the device (and takes acc.dev() of a field
+// of the decoder's own); it is called only when a field is requested.
+template <class Upload, class Decode>
+static void decoder_run(dsce_ctx* ctx, Scheme& s, int32_t id, uint64_t seed, uint64_t first_rep, uint64_t n_rep, uint32_t flags,
+                 const char* what, CountAcc& acc, CodewordK& cw, Upload upload, Decode decode) {
+    const bool perfect = (flags & DSCE_LLR_PERFECT) != 0, maxlog = (flags & DSCE_LLR_MAXLOG) != 0;
+    const int nsnr = ctx->nsnr, S = ctx->niter + 1, m = s.d.bits_per_symbol;
+    const size_t B = (size_t)s.d.n_data * m;
+    const int chunk = snr_chunk(ctx);
+    const size_t extra = (S * B * sizeof(double) * (size_t)nsnr + chunk - 1) / chunk;
+    const int rsub = bulk_sub_batch(ctx, s, perfect, extra);
+    ExportSink sink = acc.sink(what);
+    DeviceTemps tmp(ctx);
+    double* dllr = nullptr;
+    acc.alloc(ctx, tmp);
+    if (acc.block) {
+        upload(tmp);
+        if (n_rep > 0) dllr = tmp.alloc<double>((size_t)rsub * nsnr * S * B);
+    }
+    cw.acc_bit = acc.dev(0);
+    cw.acc_frame = acc.dev(1);
+    cw.m = m;
+    cw.B = (int)B;
+    cw.S = S;
+    cw.nsnr = nsnr;
+    bulk_export(ctx, s, id, seed, first_rep, n_rep, sink, [&](const Bulk& bk, int snr0) {
+        LlrK a = llr_args(ctx, s, bk, snr0, maxlog, perfect);
+        if (a.R > rsub || a.rvalid > a.R) throw ApiError(DSCE_EINVAL, std::string(what) + ": LLR temporary too small");
+        a.row0 = 0;
+        a.out[2] = dllr;
+        {
+            Timed t(ctx, "k_llr");
+            launch_llr(ctx->stream, a, false);
+        }
+        cw.llr = dllr;
+        cw.sidx = ctx->buf.sidx;
+        cw.R = a.R;
+        cw.snr0 = snr0;
+        cw.nchunk = a.U / a.R;
+        cw.ncw = (long long)a.rvalid * cw.nchunk * S;
+        decode();
+        DSCE_HIP_CHECK(hipGetLastError());
+    }, perfect, extra);
+    if (n_rep > 0) acc.add_back(ctx);
+    tmp.release_checked();
+}
+
+// The call behind dsce_viterbi and dsce_ldpc: a decoder on the caller's lam
+// [n_cw][n_slots].  check() is the entry point's check of its code against
+// n_slots; launch(tmp, dlam) uploads the code tables, allocates the outputs,
+// launches the probe kernel under its Timed name and returns the callable that
+// queues the copies back.  `out` is the output the call cannot do without.
+// Needs only the context.
+template <class Check, class Launch>
+static void decoder_probe(dsce_ctx* ctx, const char* what, int64_t n_slots, const double* lam, int64_t n_cw, const void* out,
+                   Check check, Launch launch) {
+    const std::string w(what);
+    if (n_slots < 0) throw ApiError(DSCE_EINVAL, w + ": n_slots < 0");
+    check();
+    if (n_cw < 0) throw ApiError(DSCE_EINVAL, w + ": n_cw < 0");
+    if (n_cw > 0 && (!lam || !out)) throw ApiError(DSCE_EINVAL, w + ": null pointer");
+    if (n_cw == 0) return;
+    const size_t nl = (size_t)n_cw * (size_t)n_slots;
+    DeviceTemps tmp(ctx);
+    double* dlam = tmp.alloc<double>(nl);
+    if (nl) DSCE_HIP_CHECK(hipMemcpyAsync(dlam, lam, nl * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    auto fetch = launch(tmp, dlam);
+    DSCE_HIP_CHECK(hipGetLastError());
+    fetch();
+    tmp.release_checked();
+    if (ctx->timing) collect_timing(ctx);
+}
+
+}  // extern "C++"
 
 // The checks of a code table against n_slots slots (dsce_run_coded, dsce_viterbi)
 static void check_code(const dsce_code_desc* code, int64_t n_slots, const std::string& w) {
@@ -3087,112 +3215,55 @@ static void check_code(const dsce_code_desc* code, int64_t n_slots, const std::s
             throw ApiError(DSCE_EINVAL, w + ": src entry outside [-1, slots)");
 }
 
-// Coded bit and frame errors (DSCE_HAS_CODED_RUN): dsce_run_soft's run with a
-// decoder in place of the sum.  After each SNR chunk k_llr, unmodified and in its
-// fp64 instance with llr only, writes the chunk's LLRs into a device temporary in
-// the export layout, [rsub][n_snr][S][ND m] with row0 = 0 (k_llr indexes by the
-// absolute SNR index, so the temporary has every SNR row; its bytes per unit count
-// towards export_stage_mb): the bits of dsce_export_llr.  k_viterbi then decodes
-// one codeword per wave and adds its counts to int64 device accumulators that live
-// for the call (declared before bulk_export's temporaries, so they outlive its
-// stream wait); they are added into the caller's arrays once.
+// src [T][2] of a checked code table on the device, for the call
+static const int* upload_code(dsce_ctx* ctx, DeviceTemps& tmp, const dsce_code_desc* code) {
+    const size_t n = 2 * (size_t)code->n_steps;
+    int* dsrc = tmp.alloc<int>(n);
+    DSCE_HIP_CHECK(hipMemcpyAsync(dsrc, code->src, n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    return dsrc;
+}
+
+// Coded bit and frame errors (DSCE_HAS_CODED_RUN): decoder_run with k_viterbi,
+// one wave per codeword.
 int dsce_run_coded(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, uint64_t n_rep, uint32_t flags,
                    const dsce_code_desc* code, const dsce_coded_out* out) {
     TraceRange trace_range("dsce run coded");
     API_BEGIN
     check_ctx(ctx);
     Scheme& s = bulk_export_check(ctx, id, out, flags, DSCE_LLR_MAXLOG | DSCE_LLR_PERFECT, "dsce_run_coded");
-    const bool perfect = (flags & DSCE_LLR_PERFECT) != 0, maxlog = (flags & DSCE_LLR_MAXLOG) != 0;
-    const int ND = s.d.n_data, nsnr = ctx->nsnr, S = ctx->niter + 1, m = s.d.bits_per_symbol;
-    const size_t B = (size_t)ND * m;
-    check_code(code, (int64_t)B, "dsce_run_coded");
-    ExportSink sink{"dsce_run_coded", 2, {out->bit_err, out->frame_err}, {0, 0}, {sizeof(int64_t), sizeof(int64_t)}, false};
-    const size_t ncell = (size_t)nsnr * S;
-    const bool any = out->bit_err || out->frame_err;
-    const int chunk = snr_chunk(ctx);
-    const size_t extra = (S * B * sizeof(double) * (size_t)nsnr + chunk - 1) / chunk;
-    const int rsub = bulk_sub_batch(ctx, s, perfect, extra);
-    std::vector<unsigned long long> host(2 * ncell);
-    DeviceTemps tmp(ctx);
+    check_code(code, (int64_t)s.d.n_data * s.d.bits_per_symbol, "dsce_run_coded");
+    const size_t ncell = (size_t)ctx->nsnr * (ctx->niter + 1);
+    CountAcc acc{{out->bit_err, ncell}, {out->frame_err, ncell}};
     CodedK q{};
-    double* dllr = nullptr;
-    if (any) {
-        // no field requested: bulk_export refuses below, before anything is launched
-        unsigned long long* acc = tmp.alloc<unsigned long long>(2 * ncell);
-        DSCE_HIP_CHECK(hipMemsetAsync(acc, 0, 2 * ncell * sizeof(unsigned long long), ctx->stream));
-        q.acc_bit = out->bit_err ? acc : nullptr;
-        q.acc_frame = out->frame_err ? acc + ncell : nullptr;
-        int* dsrc = tmp.alloc<int>(2 * (size_t)code->n_steps);
-        DSCE_HIP_CHECK(hipMemcpyAsync(dsrc, code->src, 2 * (size_t)code->n_steps * sizeof(int), hipMemcpyHostToDevice,
-                                      ctx->stream));
-        q.src = dsrc;
-        if (n_rep > 0) dllr = tmp.alloc<double>((size_t)rsub * nsnr * S * B);
-    }
     q.T = code->n_steps;
     q.terminated = code->terminated ? 1 : 0;
     q.wpb = viterbi_waves_per_block(q.T);
-    q.m = m;
-    q.B = (int)B;
-    q.S = S;
-    q.nsnr = nsnr;
-    bulk_export(ctx, s, id, seed, first_rep, n_rep, sink, [&](const Bulk& bk, int snr0) {
-        LlrK a = llr_args(ctx, s, bk, snr0, maxlog, perfect);
-        if (a.R > rsub || a.rvalid > a.R) throw ApiError(DSCE_EINVAL, "dsce_run_coded: LLR temporary too small");
-        a.row0 = 0;
-        a.out[2] = dllr;
-        {
-            Timed t(ctx, "k_llr");
-            launch_llr(ctx->stream, a, false);
-        }
-        q.llr = dllr;
-        q.sidx = ctx->buf.sidx;
-        q.R = a.R;
-        q.snr0 = snr0;
-        q.nchunk = a.U / a.R;
-        q.ncw = (long long)a.rvalid * q.nchunk * S;
-        Timed t(ctx, "k_viterbi");
-        launch_viterbi(ctx->stream, q);
-        DSCE_HIP_CHECK(hipGetLastError());
-    }, perfect, extra);
-    if (n_rep > 0 && any) {
-        const unsigned long long* from = q.acc_bit ? q.acc_bit : q.acc_frame - ncell;
-        DSCE_HIP_CHECK(hipMemcpyAsync(host.data(), from, host.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                                      ctx->stream));
-        DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        for (size_t i = 0; out->bit_err && i < ncell; ++i) out->bit_err[i] += (int64_t)host[i];
-        for (size_t i = 0; out->frame_err && i < ncell; ++i) out->frame_err[i] += (int64_t)host[ncell + i];
-    }
-    tmp.release_checked();
+    decoder_run(ctx, s, id, seed, first_rep, n_rep, flags, "dsce_run_coded", acc, q.cw,
+                [&](DeviceTemps& tmp) { q.src = upload_code(ctx, tmp, code); },
+                [&] {
+                    Timed t(ctx, "k_viterbi");
+                    launch_viterbi(ctx->stream, q);
+                });
     API_END
 }
 
 // The decoder of dsce_run_coded on the caller's lam: k_viterbi_probe, the same
-// device function with another load and store.  Needs only the context.
+// device function with another load and store.
 int dsce_viterbi(dsce_ctx* ctx, const dsce_code_desc* code, int64_t n_slots, const double* lam, int64_t n_cw,
                  uint8_t* info_out) {
     API_BEGIN
     check_ctx(ctx);
-    if (n_slots < 0) throw ApiError(DSCE_EINVAL, "dsce_viterbi: n_slots < 0");
-    check_code(code, n_slots, "dsce_viterbi");
-    if (n_cw < 0) throw ApiError(DSCE_EINVAL, "dsce_viterbi: n_cw < 0");
-    if (n_cw > 0 && (!lam || !info_out)) throw ApiError(DSCE_EINVAL, "dsce_viterbi: null pointer");
-    if (n_cw > 0) {
-        const size_t T = (size_t)code->n_steps, nl = (size_t)n_cw * (size_t)n_slots;
-        DeviceTemps tmp(ctx);
-        int* dsrc = tmp.alloc<int>(2 * T);
-        double* dlam = tmp.alloc<double>(nl);
-        uint8_t* dout = tmp.alloc<uint8_t>((size_t)n_cw * T);
-        DSCE_HIP_CHECK(hipMemcpyAsync(dsrc, code->src, 2 * T * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        if (nl) DSCE_HIP_CHECK(hipMemcpyAsync(dlam, lam, nl * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        {
-            Timed t(ctx, "k_viterbi");
-            launch_viterbi_probe(ctx->stream, dsrc, (int)T, code->terminated ? 1 : 0, n_cw, n_slots, dlam, dout);
-        }
-        DSCE_HIP_CHECK(hipGetLastError());
-        DSCE_HIP_CHECK(hipMemcpyAsync(info_out, dout, (size_t)n_cw * T, hipMemcpyDeviceToHost, ctx->stream));
-        tmp.release_checked();
-        if (ctx->timing) collect_timing(ctx);
-    }
+    decoder_probe(ctx, "dsce_viterbi", n_slots, lam, n_cw, info_out, [&] { check_code(code, n_slots, "dsce_viterbi"); },
+                  [&](DeviceTemps& tmp, const double* dlam) {
+                      const size_t T = (size_t)code->n_steps;
+                      const int* dsrc = upload_code(ctx, tmp, code);
+                      uint8_t* dout = tmp.alloc<uint8_t>((size_t)n_cw * T);
+                      Timed t(ctx, "k_viterbi");
+                      launch_viterbi_probe(ctx->stream, dsrc, (int)T, code->terminated ? 1 : 0, n_cw, n_slots, dlam, dout);
+                      return [=] {
+                          DSCE_HIP_CHECK(hipMemcpyAsync(info_out, dout, (size_t)n_cw * T, hipMemcpyDeviceToHost, ctx->stream));
+                      };
+                  });
     API_END
 }
 
@@ -3271,104 +3342,50 @@ static LdpcCodeK upload_ldpc(dsce_ctx* ctx, DeviceTemps& tmp, const dsce_ldpc_de
 }
 
 // Coded bit and frame errors and iteration counts of a min-sum LDPC decoder
-// (DSCE_HAS_LDPC_RUN): dsce_run_coded's run (the same k_llr temporary, the same
-// sub-batches) with k_ldpc, one workgroup per codeword, in place of k_viterbi.
+// (DSCE_HAS_LDPC_RUN): decoder_run with k_ldpc, one workgroup per codeword.
 int dsce_run_ldpc(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, uint64_t n_rep, uint32_t flags,
                   const dsce_ldpc_desc* code, const dsce_ldpc_out* out) {
     TraceRange trace_range("dsce run ldpc");
     API_BEGIN
     check_ctx(ctx);
     Scheme& s = bulk_export_check(ctx, id, out, flags, DSCE_LLR_MAXLOG | DSCE_LLR_PERFECT, "dsce_run_ldpc");
-    const bool perfect = (flags & DSCE_LLR_PERFECT) != 0, maxlog = (flags & DSCE_LLR_MAXLOG) != 0;
-    const int ND = s.d.n_data, nsnr = ctx->nsnr, S = ctx->niter + 1, m = s.d.bits_per_symbol;
-    const size_t B = (size_t)ND * m;
-    check_ldpc(ctx, code, (int64_t)B, "dsce_run_ldpc");
-    ExportSink sink{"dsce_run_ldpc", 3, {out->bit_err, out->frame_err, out->iter_sum}, {0, 0, 0},
-                    {sizeof(int64_t), sizeof(int64_t), sizeof(int64_t)}, false};
-    const size_t ncell = (size_t)nsnr * S;
-    const bool any = out->bit_err || out->frame_err || out->iter_sum;
-    const int chunk = snr_chunk(ctx);
-    const size_t extra = (S * B * sizeof(double) * (size_t)nsnr + chunk - 1) / chunk;
-    const int rsub = bulk_sub_batch(ctx, s, perfect, extra);
-    std::vector<unsigned long long> host(3 * ncell);
-    DeviceTemps tmp(ctx);
+    check_ldpc(ctx, code, (int64_t)s.d.n_data * s.d.bits_per_symbol, "dsce_run_ldpc");
+    const size_t ncell = (size_t)ctx->nsnr * (ctx->niter + 1);
+    CountAcc acc{{out->bit_err, ncell}, {out->frame_err, ncell}, {out->iter_sum, ncell}};
     LdpcK q{};
-    unsigned long long* acc = nullptr;
-    double* dllr = nullptr;
-    if (any) {
-        // no field requested: bulk_export refuses below, before anything is launched
-        acc = tmp.alloc<unsigned long long>(3 * ncell);
-        DSCE_HIP_CHECK(hipMemsetAsync(acc, 0, 3 * ncell * sizeof(unsigned long long), ctx->stream));
-        q.acc_bit = out->bit_err ? acc : nullptr;
-        q.acc_frame = out->frame_err ? acc + ncell : nullptr;
-        q.acc_iter = out->iter_sum ? acc + 2 * ncell : nullptr;
-        q.c = upload_ldpc(ctx, tmp, code);
-        if (n_rep > 0) dllr = tmp.alloc<double>((size_t)rsub * nsnr * S * B);
-    }
-    q.m = m;
-    q.B = (int)B;
-    q.S = S;
-    q.nsnr = nsnr;
-    bulk_export(ctx, s, id, seed, first_rep, n_rep, sink, [&](const Bulk& bk, int snr0) {
-        LlrK a = llr_args(ctx, s, bk, snr0, maxlog, perfect);
-        if (a.R > rsub || a.rvalid > a.R) throw ApiError(DSCE_EINVAL, "dsce_run_ldpc: LLR temporary too small");
-        a.row0 = 0;
-        a.out[2] = dllr;
-        {
-            Timed t(ctx, "k_llr");
-            launch_llr(ctx->stream, a, false);
-        }
-        q.llr = dllr;
-        q.sidx = ctx->buf.sidx;
-        q.R = a.R;
-        q.snr0 = snr0;
-        q.nchunk = a.U / a.R;
-        q.ncw = (long long)a.rvalid * q.nchunk * S;
-        Timed t(ctx, "k_ldpc");
-        launch_ldpc(ctx->stream, q);
-        DSCE_HIP_CHECK(hipGetLastError());
-    }, perfect, extra);
-    if (n_rep > 0 && any) {
-        DSCE_HIP_CHECK(hipMemcpyAsync(host.data(), acc, host.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                                      ctx->stream));
-        DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        for (size_t i = 0; out->bit_err && i < ncell; ++i) out->bit_err[i] += (int64_t)host[i];
-        for (size_t i = 0; out->frame_err && i < ncell; ++i) out->frame_err[i] += (int64_t)host[ncell + i];
-        for (size_t i = 0; out->iter_sum && i < ncell; ++i) out->iter_sum[i] += (int64_t)host[2 * ncell + i];
-    }
-    tmp.release_checked();
+    decoder_run(ctx, s, id, seed, first_rep, n_rep, flags, "dsce_run_ldpc", acc, q.cw,
+                [&](DeviceTemps& tmp) {
+                    q.acc_iter = acc.dev(2);
+                    q.c = upload_ldpc(ctx, tmp, code);
+                },
+                [&] {
+                    Timed t(ctx, "k_ldpc");
+                    launch_ldpc(ctx->stream, q);
+                });
     API_END
 }
 
 // The decoder of dsce_run_ldpc on the caller's lam: k_ldpc_probe, the same device
-// function with another load and store.  Needs only the context.
+// function with another load and store.
 int dsce_ldpc(dsce_ctx* ctx, const dsce_ldpc_desc* code, int64_t n_slots, const double* lam, int64_t n_cw,
               uint8_t* bits_out, int32_t* iters_out) {
     API_BEGIN
     check_ctx(ctx);
-    if (n_slots < 0) throw ApiError(DSCE_EINVAL, "dsce_ldpc: n_slots < 0");
-    check_ldpc(ctx, code, n_slots, "dsce_ldpc");
-    if (n_cw < 0) throw ApiError(DSCE_EINVAL, "dsce_ldpc: n_cw < 0");
-    if (n_cw > 0 && (!lam || !bits_out)) throw ApiError(DSCE_EINVAL, "dsce_ldpc: null pointer");
-    if (n_cw > 0) {
-        const size_t N = (size_t)code->n_vars, nl = (size_t)n_cw * (size_t)n_slots;
-        DeviceTemps tmp(ctx);
-        const LdpcCodeK k = upload_ldpc(ctx, tmp, code);
-        double* dlam = tmp.alloc<double>(std::max<size_t>(nl, 1));
-        uint8_t* dbits = tmp.alloc<uint8_t>((size_t)n_cw * N);
-        int* dit = tmp.alloc<int>((size_t)n_cw);
-        if (nl) DSCE_HIP_CHECK(hipMemcpyAsync(dlam, lam, nl * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        {
-            Timed t(ctx, "k_ldpc");
-            launch_ldpc_probe(ctx->stream, k, n_cw, n_slots, dlam, dbits, dit);
-        }
-        DSCE_HIP_CHECK(hipGetLastError());
-        DSCE_HIP_CHECK(hipMemcpyAsync(bits_out, dbits, (size_t)n_cw * N, hipMemcpyDeviceToHost, ctx->stream));
-        if (iters_out)
-            DSCE_HIP_CHECK(hipMemcpyAsync(iters_out, dit, (size_t)n_cw * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        tmp.release_checked();
-        if (ctx->timing) collect_timing(ctx);
-    }
+    decoder_probe(ctx, "dsce_ldpc", n_slots, lam, n_cw, bits_out, [&] { check_ldpc(ctx, code, n_slots, "dsce_ldpc"); },
+                  [&](DeviceTemps& tmp, const double* dlam) {
+                      const size_t N = (size_t)code->n_vars;
+                      const LdpcCodeK k = upload_ldpc(ctx, tmp, code);
+                      uint8_t* dbits = tmp.alloc<uint8_t>((size_t)n_cw * N);
+                      int* dit = tmp.alloc<int>((size_t)n_cw);
+                      Timed t(ctx, "k_ldpc");
+                      launch_ldpc_probe(ctx->stream, k, n_cw, n_slots, dlam, dbits, dit);
+                      return [=] {
+                          DSCE_HIP_CHECK(hipMemcpyAsync(bits_out, dbits, (size_t)n_cw * N, hipMemcpyDeviceToHost, ctx->stream));
+                          if (iters_out)
+                              DSCE_HIP_CHECK(hipMemcpyAsync(iters_out, dit, (size_t)n_cw * sizeof(int), hipMemcpyDeviceToHost,
+                                                            ctx->stream));
+                      };
+                  });
     API_END
 }
 

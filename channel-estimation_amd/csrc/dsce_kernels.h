@@ -412,24 +412,60 @@ struct LlrCalibK {
     double* acc_perf;         // [nsnr][ND], or null
 };
 void launch_llr_calib(hipStream_t s, const LlrCalibK& a);
-// K = 7 Viterbi decoder of one sub-batch and SNR chunk after k_llr (k_viterbi,
-// kernels_viterbi.hip; dsce_run_coded): one wave per codeword = (realisation rl <
-// rvalid, SNR point of the chunk, stage), ncw = rvalid nchunk S of them, stage
-// fastest.  llr is k_llr's fp64 output with row0 = 0, [R][nsnr][S][B], B = ND m;
-// the decoder input of slot j m + b is that LLR, negated where bit b of
-// sidx[j][rl] is 1.  src [T][2] holds slots in [-1, B) (checked by the host).  The
-// decoded ones among the first T - 6 (terminated) or T inputs are added to
-// acc_bit[snr][stage], and 1 to acc_frame[snr][stage] if there are any, with
-// integer atomics.  wpb waves per block, each with T decision words of LDS.
-struct CodedK {
-    const int* src;           // [T][2]
-    int T, terminated, wpb;
+// What a decoder after k_llr reads about the codewords of one sub-batch and SNR
+// chunk (k_viterbi / dsce_run_coded, k_ldpc / dsce_run_ldpc): codeword cw =
+// (realisation rl < rvalid, SNR point of the chunk, stage), ncw = rvalid nchunk S
+// of them, stage fastest.  llr is k_llr's fp64 output with row0 = 0,
+// [R][nsnr][S][B], B = ND m; lam of slot j m + b is that LLR, negated where bit b
+// of sidx[j][rl] is 1.  A codeword's decoded ones among its information bits are
+// added to acc_bit[snr][stage], and 1 to acc_frame[snr][stage] if there are any,
+// with integer atomics: the result does not depend on the order.
+struct CodewordK {
     long long ncw;
     const double* llr;        // [R][nsnr][S][B]
     const uint16_t* sidx;     // [ND][R] transmitted symbol indices
     int m, B, S, R, nsnr, snr0, nchunk;
     unsigned long long* acc_bit;     // [nsnr][S], or null
     unsigned long long* acc_frame;   // [nsnr][S], or null
+};
+// Where codeword cw of a CodewordK lies.  rl is kept widened: as an int the
+// compiler extends it again at every load of codeword_lam, which moved k_ldpc's
+// iteration loop by 8 bytes and cost 1.5 %.
+struct CodewordAt {
+    size_t cell;              // snr S + stage: the codeword's entry of the accumulators
+    size_t rl;                // its realisation of the sub-batch
+    const double* llr;        // its row [B] of llr
+};
+__device__ __forceinline__ CodewordAt codeword_at(const CodewordK& q, long long cw) {
+    const int stage = (int)(cw % q.S);
+    const int snr = q.snr0 + (int)((cw / q.S) % q.nchunk);
+    const int rl = (int)(cw / ((long long)q.S * q.nchunk));   // < rvalid: padding realisations are not decoded
+    CodewordAt at;
+    at.cell = (size_t)snr * q.S + stage;
+    at.llr = q.llr + (((size_t)rl * q.nsnr + snr) * q.S + stage) * (size_t)q.B;
+    at.rl = rl;
+    return at;
+}
+// lam of a slot of the codeword, signed against the transmitted bit
+__device__ __forceinline__ double codeword_lam(const CodewordK& q, const CodewordAt& at, int slot) {
+    const int j = slot / q.m, b = slot - j * q.m;
+    const double v = at.llr[slot];
+    const unsigned t = q.sidx[(size_t)j * q.R + at.rl];
+    return (t >> b) & 1u ? -v : v;
+}
+// the codeword's error count into acc_bit / acc_frame; one thread per codeword calls it
+__device__ __forceinline__ void codeword_count(const CodewordK& q, const CodewordAt& at, int errs) {
+    if (q.acc_bit && errs) atomicAdd(q.acc_bit + at.cell, (unsigned long long)errs);
+    if (q.acc_frame && errs) atomicAdd(q.acc_frame + at.cell, 1ull);
+}
+// K = 7 Viterbi decoder after k_llr (k_viterbi, kernels_viterbi.hip;
+// dsce_run_coded): one wave per codeword of cw.  src [T][2] holds slots in
+// [-1, B) (checked by the host); the information bits are the first T - 6
+// (terminated) or T inputs.  wpb waves per block, each with T decision words of LDS.
+struct CodedK {
+    const int* src;           // [T][2]
+    int T, terminated, wpb;
+    CodewordK cw;
 };
 constexpr int CODE_MAX_STEPS = 8192;  // DSCE_CODE_MAX_STEPS: 8 bytes of decisions per step, 64 KiB per block
 inline int viterbi_waves_per_block(int T) { return std::max(1, std::min(4, CODE_MAX_STEPS / std::max(T, 1))); }
@@ -453,18 +489,11 @@ struct LdpcCodeK {
     double alpha;
 };
 inline size_t ldpc_lds_bytes(int N, int M) { return (size_t)N * 8 + (size_t)M * 24 + 8; }
-// k_ldpc after k_llr (dsce_run_ldpc): codeword = (realisation rl < rvalid, SNR point of the chunk, stage) as in
-// CodedK, ncw = rvalid nchunk S blocks; ell of slot j m + b is -lam, lam = k_llr's LLR negated where bit b of
-// sidx[j][rl] is 1.  The decoded ones among the first n_info variables go to acc_bit[snr][stage], 1 to acc_frame if
-// there are any, and the iterations performed to acc_iter, by integer atomics.
+// k_ldpc after k_llr (dsce_run_ldpc): one block per codeword of cw, ell = -lam.  The information bits are the first
+// n_info variables; the iterations performed go to acc_iter[snr][stage] by an integer atomic as well.
 struct LdpcK {
     LdpcCodeK c;
-    long long ncw;
-    const double* llr;        // [R][nsnr][S][B]
-    const uint16_t* sidx;     // [ND][R] transmitted symbol indices
-    int m, B, S, R, nsnr, snr0, nchunk;
-    unsigned long long* acc_bit;     // [nsnr][S], or null
-    unsigned long long* acc_frame;   // [nsnr][S], or null
+    CodewordK cw;
     unsigned long long* acc_iter;    // [nsnr][S], or null
 };
 void launch_ldpc(hipStream_t s, const LdpcK& a);

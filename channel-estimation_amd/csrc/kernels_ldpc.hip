@@ -22,6 +22,7 @@
 // check raises one of two alternating LDS flag words, and every thread reads it
 // after the barrier, so the exit is block-uniform and costs one check phase.
 // fp64 in the order of include/dsce.h, no FMA (-ffp-contract=off), no clipping.
+#include "dsce_dispatch.h"
 #include "dsce_kernels.h"
 
 #include <math.h>
@@ -140,28 +141,15 @@ __device__ __forceinline__ int ldpc_block(const LdpcCodeK& c, const LdpcLds& l, 
     return it;
 }
 
-// k_ldpc — block = codeword (realisation rl < rvalid of the sub-batch, SNR point of
-// the chunk, stage), as k_viterbi's waves.  lam of slot i = j m + b: the LLR k_llr
-// wrote, negated where bit b of the transmitted symbol sidx[j][rl] is 1; ell =
-// -lam.  The block's counts go to the call's int64 accumulators by one integer
-// atomic each: the result does not depend on the order.
+// k_ldpc — one block per codeword of q.cw (CodewordK: placement, lam, counts), ell = -lam.
 template <int VPT>
 __global__ void __launch_bounds__(1024) k_ldpc(LdpcK q) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ldpc_lds[];
     const LdpcLds l = ldpc_carve(ldpc_lds, q.c.N, q.c.M);
-    const long long cw = blockIdx.x;
-    const int stage = (int)(cw % q.S);
-    const int sc = (int)((cw / q.S) % q.nchunk);
-    const int rl = (int)(cw / ((long long)q.S * q.nchunk));   // < rvalid: padding realisations are not decoded
-    const int snr = q.snr0 + sc;
-    const double* llr = q.llr + (((size_t)rl * q.nsnr + snr) * q.S + stage) * (size_t)q.B;
+    const CodewordAt at = codeword_at(q.cw, blockIdx.x);
     const int it = ldpc_block<VPT>(q.c, l, [&](int v) {
         const int slot = q.c.slot[v];
-        if (slot < 0) return 0.0;
-        const int j = slot / q.m, b = slot - j * q.m;
-        const double val = llr[slot];
-        const unsigned t = q.sidx[(size_t)j * q.R + rl];
-        return (t >> b) & 1u ? val : -val;
+        return slot < 0 ? 0.0 : -codeword_lam(q.cw, at, slot);
     });
     int errs = 0;
     for (int v = threadIdx.x; v < q.c.n_info; v += blockDim.x) errs += l.P[v] < 0.0 ? 1 : 0;
@@ -171,11 +159,8 @@ __global__ void __launch_bounds__(1024) k_ldpc(LdpcK q) {
     if (errs) atomicAdd(l.flag, errs);
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int total = l.flag[0];
-        const size_t cell = (size_t)snr * q.S + stage;
-        if (q.acc_bit && total) atomicAdd(q.acc_bit + cell, (unsigned long long)total);
-        if (q.acc_frame && total) atomicAdd(q.acc_frame + cell, 1ull);
-        if (q.acc_iter) atomicAdd(q.acc_iter + cell, (unsigned long long)it);
+        codeword_count(q.cw, at, l.flag[0]);
+        if (q.acc_iter) atomicAdd(q.acc_iter + at.cell, (unsigned long long)it);
     }
 }
 
@@ -209,39 +194,22 @@ static void ldpc_lds_attr(K kernel, size_t lds) {
                                  hipGetErrorString(e));
 }
 
-template <int VPT>
-static void ldpc_go(hipStream_t s, const LdpcK& a, int nt, size_t lds) {
-    ldpc_lds_attr(k_ldpc<VPT>, lds);
-    hipLaunchKernelGGL(k_ldpc<VPT>, dim3((unsigned)a.ncw), dim3(nt), lds, s, a);
-}
-
-template <int VPT>
-static void ldpc_probe_go(hipStream_t s, const LdpcCodeK& c, int nt, size_t lds, long long ncw, long long n_slots,
-                          const double* lam, uint8_t* bits, int* iters) {
-    ldpc_lds_attr(k_ldpc_probe<VPT>, lds);
-    hipLaunchKernelGGL(k_ldpc_probe<VPT>, dim3((unsigned)ncw), dim3(nt), lds, s, c, n_slots, lam, bits, iters);
-}
-
 // the instance whose VPT covers ceil(N / threads): 1, 2, 4, 8, 16 registers of ell, 0 = ell read again
-#define DSCE_LDPC_VPT(CALL)                                                                      \
-    do {                                                                                         \
-        const int vpt = (c.N + nt - 1) / nt;                                                     \
-        if (vpt <= 1) CALL(1);                                                                   \
-        else if (vpt <= 2) CALL(2);                                                              \
-        else if (vpt <= 4) CALL(4);                                                              \
-        else if (vpt <= 8) CALL(8);                                                              \
-        else if (vpt <= 16) CALL(16);                                                            \
-        else CALL(0);                                                                            \
-    } while (0)
+static int ldpc_vpt(const LdpcCodeK& c, int nt) {
+    const int need = (c.N + nt - 1) / nt;
+    for (int v : {1, 2, 4, 8, 16})
+        if (need <= v) return v;
+    return 0;
+}
 
 void launch_ldpc(hipStream_t s, const LdpcK& a) {
-    if (a.ncw <= 0) return;
-    const LdpcCodeK& c = a.c;
-    const int nt = ldpc_threads(c);
-    const size_t lds = ldpc_lds_bytes(c.N, c.M);
-#define CALL(V) ldpc_go<V>(s, a, nt, lds)
-    DSCE_LDPC_VPT(CALL);
-#undef CALL
+    if (a.cw.ncw <= 0) return;
+    const int nt = ldpc_threads(a.c);
+    const size_t lds = ldpc_lds_bytes(a.c.N, a.c.M);
+    for_value<1, 2, 4, 8, 16, 0>(ldpc_vpt(a.c, nt), [&](auto VPT) {
+        ldpc_lds_attr(k_ldpc<VPT>, lds);
+        hipLaunchKernelGGL(k_ldpc<VPT>, dim3((unsigned)a.cw.ncw), dim3(nt), lds, s, a);
+    });
 }
 
 void launch_ldpc_probe(hipStream_t s, const LdpcCodeK& c, long long ncw, long long n_slots, const double* lam,
@@ -249,9 +217,10 @@ void launch_ldpc_probe(hipStream_t s, const LdpcCodeK& c, long long ncw, long lo
     if (ncw <= 0) return;
     const int nt = ldpc_threads(c);
     const size_t lds = ldpc_lds_bytes(c.N, c.M);
-#define CALL(V) ldpc_probe_go<V>(s, c, nt, lds, ncw, n_slots, lam, bits, iters)
-    DSCE_LDPC_VPT(CALL);
-#undef CALL
+    for_value<1, 2, 4, 8, 16, 0>(ldpc_vpt(c, nt), [&](auto VPT) {
+        ldpc_lds_attr(k_ldpc_probe<VPT>, lds);
+        hipLaunchKernelGGL(k_ldpc_probe<VPT>, dim3((unsigned)ncw), dim3(nt), lds, s, c, n_slots, lam, bits, iters);
+    });
 }
 
 }  // namespace dsce

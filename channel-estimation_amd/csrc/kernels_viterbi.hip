@@ -109,46 +109,29 @@ __device__ __forceinline__ void viterbi_wave(const int* __restrict__ src, int T,
     }
 }
 
-// k_viterbi — one wave per codeword (realisation rl < rvalid of the sub-batch, SNR
-// point of the chunk, stage).  lam of slot i = j m + b: the LLR k_llr wrote for
-// the codeword, negated where bit b of the transmitted symbol sidx[j][rl] is 1.
-// The wave's counts go to the call's int64 accumulators by one integer atomic
-// each: the result does not depend on the order.
+// k_viterbi — one wave per codeword of q.cw (CodewordK: placement, lam, counts).
 __global__ void __launch_bounds__(256) k_viterbi(CodedK q) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long vit_dec[];
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const long long cw = (long long)blockIdx.x * q.wpb + w;
-    if (cw >= q.ncw) return;                               // wave-uniform; no block barrier below
-    const int stage = (int)(cw % q.S);
-    const int sc = (int)((cw / q.S) % q.nchunk);
-    const int rl = (int)(cw / ((long long)q.S * q.nchunk));   // < rvalid: padding realisations are not decoded
-    const int snr = q.snr0 + sc;
-    const double* llr = q.llr + (((size_t)rl * q.nsnr + snr) * q.S + stage) * (size_t)q.B;
+    if (cw >= q.cw.ncw) return;                            // wave-uniform; no block barrier below
+    const CodewordAt at = codeword_at(q.cw, cw);
     const int K = q.terminated ? q.T - 6 : q.T;
     int errs = 0;
     viterbi_wave(q.src, q.T, q.terminated, vit_dec + (size_t)w * q.T,
-                 [&](int slot) {
-                     const int j = slot / q.m, b = slot - j * q.m;
-                     const double v = llr[slot];
-                     const unsigned t = q.sidx[(size_t)j * q.R + rl];
-                     return (t >> b) & 1u ? -v : v;
-                 },
+                 [&](int slot) { return codeword_lam(q.cw, at, slot); },
                  [&](int c0, int n, unsigned long long bits) {
                      const int k = K - c0;                  // information bits from step c0 on
                      const unsigned long long mask = k >= 64 ? ~0ull : k <= 0 ? 0ull : (1ull << k) - 1ull;
                      errs += __popcll(bits & mask);
                  });
-    if (lane == 0) {
-        const size_t cell = (size_t)snr * q.S + stage;
-        if (q.acc_bit && errs) atomicAdd(q.acc_bit + cell, (unsigned long long)errs);
-        if (q.acc_frame && errs) atomicAdd(q.acc_frame + cell, 1ull);
-    }
+    if (lane == 0) codeword_count(q.cw, at, errs);
 }
 
 void launch_viterbi(hipStream_t s, const CodedK& a) {
-    if (a.ncw <= 0) return;
-    const long long blocks = (a.ncw + a.wpb - 1) / a.wpb;
+    if (a.cw.ncw <= 0) return;
+    const long long blocks = (a.cw.ncw + a.wpb - 1) / a.wpb;
     hipLaunchKernelGGL(k_viterbi, dim3((unsigned)blocks), dim3(64 * a.wpb), viterbi_lds(a.T, a.wpb), s, a);
 }
 

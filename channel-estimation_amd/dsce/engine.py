@@ -593,6 +593,31 @@ class Engine:
         return self._bulk_export("llr", sid, seed, first_rep, n_rep, fields,
                                  _TorchArrays(self, "export_llr_torch", dtype, device), method, branch)
 
+    # -- the runs that accumulate on the GPU (run_soft, run_calib, run_coded, run_ldpc) ---
+    @staticmethod
+    def _acc_out(struct, shapes, dtype, out, default, noun):
+        """(struct filled with the pointers of `out`, out) for an accumulating run:
+        `out` a dict of C-contiguous `dtype` arrays of `shapes`, or None for zeros
+        under the `default` keys; `noun` names the outputs in the messages."""
+        if out is None:
+            out = {f: np.zeros(shapes[f], dtype=dtype) for f in default}
+        o, ptr = struct(), dict(struct._fields_)
+        for f, a in out.items():
+            if f not in shapes:
+                raise ValueError("unknown %s output %r (of %s)" % (noun, f, list(shapes)))
+            if not (isinstance(a, np.ndarray) and a.dtype == dtype and a.flags.c_contiguous
+                    and a.shape == shapes[f]):
+                raise ValueError("%s must be a C-contiguous %s array of shape %s"
+                                 % (f, np.dtype(dtype).name, shapes[f]))
+            setattr(o, f, a.ctypes.data_as(ptr[f]))
+        return o, out
+
+    @staticmethod
+    def _lam_rows(lam):
+        """(lam as C-contiguous float64 [n_cw][n_slots], whether it was one codeword [n_slots])"""
+        lam = np.asarray(lam, dtype=np.float64)
+        return np.ascontiguousarray(lam.reshape(-1, lam.shape[-1])), lam.ndim == 1
+
     # -- BICM rate from the LLRs (DSCE_HAS_SOFT_RUN) --------------------------------
     def soft_shapes(self, sid):
         """Shapes of dsce_run_soft's arrays for scheme sid."""
@@ -612,17 +637,8 @@ class Engine:
         computed from zero.  bicm_rate turns a sum into a rate.  branch 'perfect'
         (DSCE_LLR_PERFECT): loss_est receives the sums of the perfect-CSI branch at
         every stage, and loss_perf0 (its stage 0) may not be given."""
-        shapes = self.soft_shapes(sid)
-        if out is None:
-            out = {f: np.zeros(shp) for f, shp in shapes.items() if branch == "mmse" or f == "loss_est"}
-        o = SoftOut()
-        for f, a in out.items():
-            if f not in shapes:
-                raise ValueError("unknown soft output %r (of %s)" % (f, list(shapes)))
-            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous
-                    and a.shape == shapes[f]):
-                raise ValueError("%s must be a C-contiguous float64 array of shape %s" % (f, shapes[f]))
-            setattr(o, f, _dptr(a))
+        o, out = self._acc_out(SoftOut, self.soft_shapes(sid), np.float64, out,
+                               ("loss_est", "loss_perf0") if branch == "mmse" else ("loss_est",), "soft")
         self._chk(self.lib.dsce_run_soft(self.h, int(sid), int(seed), int(first_rep), int(n_rep),
                                          self._llr_flag(method) | self._branch_flag(branch), C.byref(o)),
                   "dsce_run_soft")
@@ -656,17 +672,8 @@ class Engine:
         computed) and `out` is returned; without it both are computed from zero.
         branch 'perfect' (DSCE_LLR_PERFECT): ratio_est is the perfect-CSI branch's at
         every stage (rho for set_llr_scale_perf), and ratio_perf0 may not be given."""
-        shapes = self.calib_shapes(sid)
-        if out is None:
-            out = {f: np.zeros(shp) for f, shp in shapes.items() if branch == "mmse" or f == "ratio_est"}
-        o = CalibOut()
-        for f, a in out.items():
-            if f not in shapes:
-                raise ValueError("unknown calibration output %r (of %s)" % (f, list(shapes)))
-            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous
-                    and a.shape == shapes[f]):
-                raise ValueError("%s must be a C-contiguous float64 array of shape %s" % (f, shapes[f]))
-            setattr(o, f, _dptr(a))
+        o, out = self._acc_out(CalibOut, self.calib_shapes(sid), np.float64, out,
+                               ("ratio_est", "ratio_perf0") if branch == "mmse" else ("ratio_est",), "calibration")
         self._chk(self.lib.dsce_run_calib(self.h, int(sid), int(seed), int(first_rep), int(n_rep),
                                           self._branch_flag(branch), C.byref(o)), "dsce_run_calib")
         return out
@@ -734,9 +741,7 @@ class Engine:
         positive = the bit is 1) under the table of `code` (dsce.coding.make_code):
         uint8 [n_cw][n_steps] decoded inputs (dsce_viterbi), equal to the bit to
         dsce.coding.viterbi_decode.  Needs only the context."""
-        lam = np.asarray(lam, dtype=np.float64)
-        single = lam.ndim == 1
-        lam = np.ascontiguousarray(lam.reshape(-1, lam.shape[-1]))
+        lam, single = self._lam_rows(lam)
         desc, src = self._code_desc(code)
         out = np.zeros((lam.shape[0], src.shape[0]), dtype=np.uint8)
         self._chk(self.lib.dsce_viterbi(self.h, C.byref(desc), lam.shape[1], _dptr(lam), lam.shape[0],
@@ -762,16 +767,7 @@ class Engine:
         code.n_info), FER = frame_err / n_rep.  branch 'perfect'
         (DSCE_LLR_PERFECT): the LLRs of the perfect-CSI branch."""
         shapes = self.coded_shapes(sid)
-        if out is None:
-            out = {f: np.zeros(shp, dtype=np.int64) for f, shp in shapes.items()}
-        o = CodedOut()
-        for f, a in out.items():
-            if f not in shapes:
-                raise ValueError("unknown coded output %r (of %s)" % (f, list(shapes)))
-            if not (isinstance(a, np.ndarray) and a.dtype == np.int64 and a.flags.c_contiguous
-                    and a.shape == shapes[f]):
-                raise ValueError("%s must be a C-contiguous int64 array of shape %s" % (f, shapes[f]))
-            setattr(o, f, a.ctypes.data_as(C.POINTER(C.c_int64)))
+        o, out = self._acc_out(CodedOut, shapes, np.int64, out, tuple(shapes), "coded")
         desc, src = self._code_desc(code)
         self._chk(self.lib.dsce_run_coded(self.h, int(sid), int(seed), int(first_rep), int(n_rep),
                                           self._llr_flag(method) | self._branch_flag(branch), C.byref(desc),
@@ -798,9 +794,7 @@ class Engine:
         (x uint8 [n_cw][n_vars], it int32 [n_cw]), the decided bits and the
         iterations performed (dsce_ldpc), equal to the bit to
         dsce.coding.ldpc_decode.  Needs only the context."""
-        lam = np.asarray(lam, dtype=np.float64)
-        single = lam.ndim == 1
-        lam = np.ascontiguousarray(lam.reshape(-1, lam.shape[-1]))
+        lam, single = self._lam_rows(lam)
         desc, keep = self._ldpc_desc(code)
         x = np.zeros((lam.shape[0], int(code.n_vars)), dtype=np.uint8)
         it = np.zeros(lam.shape[0], dtype=np.int32)
@@ -828,16 +822,7 @@ class Engine:
         code.n_info), FER = frame_err / n_rep, mean iterations = iter_sum / n_rep.
         branch 'perfect' (DSCE_LLR_PERFECT): the LLRs of the perfect-CSI branch."""
         shapes = self.ldpc_shapes(sid)
-        if out is None:
-            out = {f: np.zeros(shp, dtype=np.int64) for f, shp in shapes.items()}
-        o = LdpcOut()
-        for f, a in out.items():
-            if f not in shapes:
-                raise ValueError("unknown ldpc output %r (of %s)" % (f, list(shapes)))
-            if not (isinstance(a, np.ndarray) and a.dtype == np.int64 and a.flags.c_contiguous
-                    and a.shape == shapes[f]):
-                raise ValueError("%s must be a C-contiguous int64 array of shape %s" % (f, shapes[f]))
-            setattr(o, f, a.ctypes.data_as(C.POINTER(C.c_int64)))
+        o, out = self._acc_out(LdpcOut, shapes, np.int64, out, tuple(shapes), "ldpc")
         desc, keep = self._ldpc_desc(code)
         self._chk(self.lib.dsce_run_ldpc(self.h, int(sid), int(seed), int(first_rep), int(n_rep),
                                          self._llr_flag(method) | self._branch_flag(branch), C.byref(desc),

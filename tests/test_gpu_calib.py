@@ -288,6 +288,26 @@ def test_calib_snr_chunks():
         whole.close()
 
 
+def test_calib_sub_batch_cuts(calib_ofdm):
+    """Realisations [0, 130): batch 128 with export_stage_mb 1 (one-wave
+    sub-batches), then with snr_chunk 1, give the batch-64 sums at rtol 1e-10 (the
+    module docstring's bar for the order of summation)."""
+    S, eng = calib_ofdm
+    eng.set_batch(64)
+    ref = _calib(eng, 0, SEED, 0, 130)
+    try:
+        eng.set_batch(128)
+        eng.set_option("export_stage_mb", 1)
+        _close(_calib(eng, 0, SEED, 0, 130), ref)
+        eng.set_option("export_stage_mb", 1024)
+        eng.set_option("snr_chunk", 1)
+        _close(_calib(eng, 0, SEED, 0, 130), ref)
+    finally:
+        eng.set_option("export_stage_mb", 1024)
+        eng.set_option("snr_chunk", 0)
+        eng.set_batch(64)
+
+
 def test_calib_errors_and_side_effects(calib_ofdm):
     from dsce import engine
     S, eng = calib_ofdm

@@ -217,6 +217,26 @@ def test_soft_snr_chunks():
         whole.close()
 
 
+def test_soft_sub_batch_cuts(soft_ofdm):
+    """Realisations [0, 130): batch 128 with export_stage_mb 1 (one-wave
+    sub-batches), then with snr_chunk 1, give the batch-64 sums at rtol 1e-10 (the
+    module docstring's bar for the order of summation)."""
+    S, eng = soft_ofdm
+    eng.set_batch(64)
+    ref = _soft(eng, 0, SEED, 0, 130)
+    try:
+        eng.set_batch(128)
+        eng.set_option("export_stage_mb", 1)
+        _close(_soft(eng, 0, SEED, 0, 130), ref)
+        eng.set_option("export_stage_mb", 1024)
+        eng.set_option("snr_chunk", 1)
+        _close(_soft(eng, 0, SEED, 0, 130), ref)
+    finally:
+        eng.set_option("export_stage_mb", 1024)
+        eng.set_option("snr_chunk", 0)
+        eng.set_batch(64)
+
+
 def test_soft_errors_and_side_effects(soft_ofdm):
     from dsce import engine
     S, eng = soft_ofdm
