@@ -3389,6 +3389,124 @@ int dsce_ldpc(dsce_ctx* ctx, const dsce_ldpc_desc* code, int64_t n_slots, const 
     API_END
 }
 
+// The checks of a layer partition against a checked description (dsce_run_ldpc_layered, dsce_ldpc_layered): every
+// check in exactly one layer, no two checks of a layer sharing a variable, in one walk over the edges.  The LDS of
+// k_ldpc_layered is k_ldpc's (ldpc_layered_lds_bytes), which check_ldpc has compared with lds_max.
+static void check_ldpc_layers(const dsce_ldpc_desc* d, const dsce_ldpc_layers* y, const std::string& w) {
+    if (!y || !y->layer_ptr || !y->layer_check) throw ApiError(DSCE_EINVAL, w + ": null layers, layer_ptr or layer_check");
+    const int M = d->n_checks, L = y->n_layers;
+    if (L < 1 || L > M) throw ApiError(DSCE_EINVAL, w + ": n_layers outside 1 .. n_checks");
+    if (y->layer_ptr[0] != 0) throw ApiError(DSCE_EINVAL, w + ": layer_ptr[0] is not 0");
+    for (int l = 0; l < L; ++l) {
+        if (y->layer_ptr[l + 1] <= y->layer_ptr[l])
+            throw ApiError(DSCE_EINVAL, w + ": layer_ptr gives layer " + std::to_string(l) + " no check");
+        if (y->layer_ptr[l + 1] > M)
+            throw ApiError(DSCE_EINVAL, w + ": layer_ptr[" + std::to_string(l + 1) + "] is beyond n_checks");
+    }
+    if (y->layer_ptr[L] != M) throw ApiError(DSCE_EINVAL, w + ": layer_ptr[n_layers] is not n_checks");
+    std::vector<char> seen((size_t)M, 0);
+    std::vector<int> stamp((size_t)d->n_vars, -1), owner((size_t)d->n_vars, 0);   // the layer that last held v, its check
+    for (int l = 0; l < L; ++l)
+        for (int i = y->layer_ptr[l]; i < y->layer_ptr[l + 1]; ++i) {
+            const int c = y->layer_check[i];
+            if (c < 0 || c >= M) throw ApiError(DSCE_EINVAL, w + ": layer_check entry outside [0, n_checks)");
+            if (seen[c]) throw ApiError(DSCE_EINVAL, w + ": check " + std::to_string(c) + " appears twice in layer_check");
+            seen[c] = 1;
+            for (int e = d->row_ptr[c]; e < d->row_ptr[c + 1]; ++e) {
+                const int v = d->col[e];
+                if (stamp[v] == l)
+                    throw ApiError(DSCE_EINVAL, w + ": layer " + std::to_string(l) + ": checks " + std::to_string(owner[v]) +
+                                                    " and " + std::to_string(c) + " share variable " + std::to_string(v));
+                stamp[v] = l;
+                owner[v] = c;
+            }
+        }
+}
+
+// The lane tables of a checked partition (LdpcLayersK), uploaded once per call
+static LdpcLayersK upload_ldpc_layers(dsce_ctx* ctx, DeviceTemps& tmp, const dsce_ldpc_desc* d, const dsce_ldpc_layers* y) {
+    const int L = y->n_layers;
+    std::vector<int> lane_ptr((size_t)L + 1, 0);
+    std::vector<int2> lane;
+    lane.reserve(2 * (size_t)d->row_ptr[d->n_checks] + 64 * (size_t)L);
+    int widest = 64;
+    for (int l = 0; l < L; ++l) {
+        for (int lg = 5; lg >= 1; --lg)                         // the groups of a layer in descending size
+            for (int i = y->layer_ptr[l]; i < y->layer_ptr[l + 1]; ++i) {
+                const int c = y->layer_check[i], e0 = d->row_ptr[c], deg = d->row_ptr[c + 1] - e0;
+                if (deg > (1 << lg) || (lg > 1 && deg <= (1 << (lg - 1)))) continue;
+                for (int p = 0; p < (1 << lg); ++p) lane.push_back(make_int2(p < deg ? d->col[e0 + p] : -1, (c << 8) | (p << 3) | lg));
+            }
+        while (lane.size() % 64) lane.push_back(make_int2(-1, 31 << 3));
+        lane_ptr[l + 1] = (int)lane.size();
+        widest = std::max(widest, lane_ptr[l + 1] - lane_ptr[l]);
+    }
+    LdpcLayersK k{};
+    int* dptr = tmp.alloc<int>(lane_ptr.size());
+    int2* dlane = tmp.alloc<int2>(lane.size());
+    DSCE_HIP_CHECK(hipMemcpyAsync(dptr, lane_ptr.data(), lane_ptr.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    DSCE_HIP_CHECK(hipMemcpyAsync(dlane, lane.data(), lane.size() * sizeof(int2), hipMemcpyHostToDevice, ctx->stream));
+    DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));      // the vectors go out of scope
+    k.lane_ptr = dptr;
+    k.lane = dlane;
+    k.n_layers = L;
+    k.threads = std::min(1024, widest);
+    return k;
+}
+
+// dsce_run_ldpc with the layered schedule (DSCE_HAS_LDPC_LAYERED): decoder_run with k_ldpc_layered.
+int dsce_run_ldpc_layered(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, uint64_t n_rep, uint32_t flags,
+                          const dsce_ldpc_desc* code, const dsce_ldpc_layers* layers, const dsce_ldpc_out* out) {
+    TraceRange trace_range("dsce run ldpc layered");
+    API_BEGIN
+    check_ctx(ctx);
+    Scheme& s = bulk_export_check(ctx, id, out, flags, DSCE_LLR_MAXLOG | DSCE_LLR_PERFECT, "dsce_run_ldpc_layered");
+    check_ldpc(ctx, code, (int64_t)s.d.n_data * s.d.bits_per_symbol, "dsce_run_ldpc_layered");
+    check_ldpc_layers(code, layers, "dsce_run_ldpc_layered");
+    const size_t ncell = (size_t)ctx->nsnr * (ctx->niter + 1);
+    CountAcc acc{{out->bit_err, ncell}, {out->frame_err, ncell}, {out->iter_sum, ncell}};
+    LdpcLayeredK q{};
+    decoder_run(ctx, s, id, seed, first_rep, n_rep, flags, "dsce_run_ldpc_layered", acc, q.cw,
+                [&](DeviceTemps& tmp) {
+                    q.acc_iter = acc.dev(2);
+                    q.c = upload_ldpc(ctx, tmp, code);
+                    q.y = upload_ldpc_layers(ctx, tmp, code, layers);
+                },
+                [&] {
+                    Timed t(ctx, "k_ldpc_layered");
+                    launch_ldpc_layered(ctx->stream, q);
+                });
+    API_END
+}
+
+// The decoder of dsce_run_ldpc_layered on the caller's lam: k_ldpc_layered_probe.
+int dsce_ldpc_layered(dsce_ctx* ctx, const dsce_ldpc_desc* code, const dsce_ldpc_layers* layers, int64_t n_slots,
+                      const double* lam, int64_t n_cw, uint8_t* bits_out, int32_t* iters_out) {
+    API_BEGIN
+    check_ctx(ctx);
+    decoder_probe(ctx, "dsce_ldpc_layered", n_slots, lam, n_cw, bits_out,
+                  [&] {
+                      check_ldpc(ctx, code, n_slots, "dsce_ldpc_layered");
+                      check_ldpc_layers(code, layers, "dsce_ldpc_layered");
+                  },
+                  [&](DeviceTemps& tmp, const double* dlam) {
+                      const size_t N = (size_t)code->n_vars;
+                      const LdpcCodeK k = upload_ldpc(ctx, tmp, code);
+                      const LdpcLayersK y = upload_ldpc_layers(ctx, tmp, code, layers);
+                      uint8_t* dbits = tmp.alloc<uint8_t>((size_t)n_cw * N);
+                      int* dit = tmp.alloc<int>((size_t)n_cw);
+                      Timed t(ctx, "k_ldpc_layered");
+                      launch_ldpc_layered_probe(ctx->stream, k, y, n_cw, n_slots, dlam, dbits, dit);
+                      return [=] {
+                          DSCE_HIP_CHECK(hipMemcpyAsync(bits_out, dbits, (size_t)n_cw * N, hipMemcpyDeviceToHost, ctx->stream));
+                          if (iters_out)
+                              DSCE_HIP_CHECK(hipMemcpyAsync(iters_out, dit, (size_t)n_cw * sizeof(int), hipMemcpyDeviceToHost,
+                                                            ctx->stream));
+                      };
+                  });
+    API_END
+}
+
 static int set_llr_scale_one(dsce_ctx* ctx, int32_t id, const double* g_est, const double* g_perf0) {
     API_BEGIN
     check_ctx(ctx);

@@ -501,6 +501,28 @@ void launch_ldpc(hipStream_t s, const LdpcK& a);
 // (k_ldpc_probe; dsce_ldpc)
 void launch_ldpc_probe(hipStream_t s, const LdpcCodeK& c, long long ncw, long long n_slots, const double* lam,
                        uint8_t* bits, int* iters);
+// The layered schedule of the same decoder (DSCE_HAS_LDPC_LAYERED; kernels_ldpc_layered.hip): the lanes of every
+// layer, built by the host from H and the checked partition.  Lane i of layer l, lane_ptr[l] <= i < lane_ptr[l + 1],
+// is lane[i] = (variable or -1, check << 8 | position << 3 | lg): a check of degree d takes 2^lg >= d consecutive
+// lanes (lg 1 .. 5) aligned to 2^lg, positions 0 .. 2^lg - 1, those >= d with variable -1; the groups of a layer
+// descend in size, and the layer is filled up to a multiple of 64 lanes with (-1, 31 << 3): lg = 0, never position 0.
+// threads = min(1024, the widest layer's lanes).  LdpcCodeK's vptr / vedge are not read.  The same LDS as k_ldpc.
+struct LdpcLayersK {
+    const int* lane_ptr;      // [n_layers + 1], multiples of 64
+    const int2* lane;         // [lane_ptr[n_layers]]
+    int n_layers, threads;
+};
+inline size_t ldpc_layered_lds_bytes(int N, int M) { return ldpc_lds_bytes(N, M); }
+struct LdpcLayeredK {
+    LdpcCodeK c;
+    LdpcLayersK y;
+    CodewordK cw;
+    unsigned long long* acc_iter;    // [nsnr][S], or null
+};
+void launch_ldpc_layered(hipStream_t s, const LdpcLayeredK& a);
+// (k_ldpc_layered_probe; dsce_ldpc_layered)
+void launch_ldpc_layered_probe(hipStream_t s, const LdpcCodeK& c, const LdpcLayersK& y, long long ncw, long long n_slots,
+                               const double* lam, uint8_t* bits, int* iters);
 // LLRs of n points x (pn: one value or one per point), out [n][m]
 void launch_llr_probe(hipStream_t s, const LlrTab& t, const double2* x, const double* pn, long long n_pn, long long n,
                       bool maxlog, double* out);

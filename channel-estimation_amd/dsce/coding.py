@@ -384,17 +384,159 @@ def ldpc_decode(lam, code, _mutate=None):
     return (x[0], its[0]) if single else (x, its)
 
 
-def ldpc_counts(llr, sym, code):
+def ldpc_counts(llr, sym, code, layers=None):
     """The definition of dsce_run_ldpc on exported arrays: llr [n][n_snr][S][ND][m]
     (export_llr) and sym [n][ND] (export) -> dict(bit_err, frame_err, iter_sum), int64
     [n_snr][S].  lam as in coded_counts; the decided information bits of the all-zero
-    codeword and the iterations performed are counted."""
+    codeword and the iterations performed are counted.  With layers = (layer_ptr,
+    layer_check) the definition of dsce_run_ldpc_layered: ldpc_decode_layered decodes."""
     llr = np.asarray(llr, dtype=np.float64)
     n, nk, S, nd, m = llr.shape
     t = ((np.asarray(sym)[..., None] >> np.arange(m)) & 1).astype(bool).reshape(n, 1, 1, nd * m)
     flat = llr.reshape(n, nk, S, nd * m)
     lam = np.where(t, -flat, flat)
-    x, it = ldpc_decode(lam.reshape(n * nk * S, nd * m), code)
+    lam = lam.reshape(n * nk * S, nd * m)
+    x, it = ldpc_decode(lam, code) if layers is None else ldpc_decode_layered(lam, code, layers)
     bit = x[:, :code.n_info].astype(np.int64).sum(axis=1)
     return dict(bit_err=bit.reshape(n, nk, S).sum(axis=0), frame_err=(bit > 0).astype(np.int64).reshape(n, nk, S).sum(axis=0),
                 iter_sum=it.astype(np.int64).reshape(n, nk, S).sum(axis=0))
+
+
+# ---- the layered schedule (include/dsce.h, DSCE_HAS_LDPC_LAYERED) ----
+
+def make_layers(code):
+    """A layer partition of the checks of `code` for dsce_run_ldpc_layered /
+    dsce_ldpc_layered by first fit in check order: check c goes to the lowest-numbered
+    layer none of whose checks shares a variable with it, else it opens a new layer.
+    Returns (layer_ptr int32 [n_layers + 1], layer_check int32 [n_checks]): the checks of
+    layer l are layer_check[layer_ptr[l] : layer_ptr[l + 1]], ascending.  Deterministic."""
+    row_ptr = np.asarray(code.row_ptr, dtype=np.int64)
+    col = np.asarray(code.col, dtype=np.int64)
+    used = [0] * int(code.n_vars)                           # per variable: bit l set = a check of layer l holds it
+    layers = []
+    for c in range(int(code.n_checks)):
+        vs = col[row_ptr[c]:row_ptr[c + 1]].tolist()
+        taken = 0
+        for v in vs:
+            taken |= used[v]
+        l = (~taken & (taken + 1)).bit_length() - 1          # the lowest clear bit
+        if l == len(layers):
+            layers.append([])
+        layers[l].append(c)
+        for v in vs:
+            used[v] |= 1 << l
+    layer_ptr = np.concatenate([[0], np.cumsum([len(x) for x in layers])]).astype(np.int32)
+    layer_check = np.array([c for x in layers for c in x], dtype=np.int32)
+    return layer_ptr, layer_check
+
+
+def serial_layers(code):
+    """One check per layer, in check order: the serial schedule, valid for every code."""
+    M = int(code.n_checks)
+    return np.arange(M + 1, dtype=np.int32), np.arange(M, dtype=np.int32)
+
+
+def check_layers(code, layers):
+    """The host's checks of a layer partition (include/dsce.h), in its order and with its
+    words: ValueError naming the offender.  Returns (layer_ptr, layer_check) as int64."""
+    if layers is None or layers[0] is None or layers[1] is None:
+        raise ValueError("null layers, layer_ptr or layer_check")
+    lp = np.asarray(layers[0], dtype=np.int64).reshape(-1)
+    lc = np.asarray(layers[1], dtype=np.int64).reshape(-1)
+    M, L = int(code.n_checks), lp.size - 1
+    if L < 1 or L > M:
+        raise ValueError("n_layers outside 1 .. n_checks")
+    if lc.size != M:
+        raise ValueError("layer_check must have n_checks entries")
+    if lp[0] != 0:
+        raise ValueError("layer_ptr[0] is not 0")
+    for l in range(L):
+        if lp[l + 1] <= lp[l]:
+            raise ValueError("layer_ptr gives layer %d no check" % l)
+    if lp[L] != M:
+        raise ValueError("layer_ptr[n_layers] is not n_checks")
+    row_ptr = np.asarray(code.row_ptr, dtype=np.int64)
+    col = np.asarray(code.col, dtype=np.int64)
+    seen = np.zeros(M, dtype=bool)
+    stamp = np.full(int(code.n_vars), -1, dtype=np.int64)   # the layer that last held the variable, and its check
+    owner = np.zeros(int(code.n_vars), dtype=np.int64)
+    for l in range(L):
+        for c in lc[lp[l]:lp[l + 1]].tolist():
+            if c < 0 or c >= M:
+                raise ValueError("layer_check entry outside [0, n_checks)")
+            if seen[c]:
+                raise ValueError("check %d appears twice in layer_check" % c)
+            seen[c] = True
+            for v in col[row_ptr[c]:row_ptr[c + 1]].tolist():
+                if stamp[v] == l:
+                    raise ValueError("layer %d: checks %d and %d share variable %d" % (l, owner[v], c, v))
+                stamp[v], owner[v] = l, c
+    return lp, lc
+
+
+def ldpc_decode_layered(lam, code, layers, _mutate=None):
+    """Layered normalised min-sum decoding of lam [n_cw][n_slots] (or [n_slots]) under
+    `code` with the layer partition `layers` = (layer_ptr, layer_check) (make_layers): (x
+    uint8 [n_cw][n_vars], it int32 [n_cw]).  The twin of k_ldpc_layered, in fp64 and in
+    the order of include/dsce.h: P = ell, R = 0; an iteration runs the layers in order,
+    and for every check of a layer, over its edge positions p, q_p = P_v - R_p, the
+    record (m1, i1, m2, sg, s_p) and R'_p exactly as in ldpc_decode, then P_v = q_p + R'_p
+    and R_p = R'_p; after the last layer x = P < 0, and with early_stop a codeword stops
+    once H x = 0.  The checks of a layer share no variable, so they are taken at once.
+    _mutate is for the tests only: 'stale' (every check reads the P of the iteration's
+    start: flooding) and 'no_store' (R' is never stored)."""
+    lp, lc = check_layers(code, layers)
+    lam = np.asarray(lam, dtype=np.float64)
+    single = lam.ndim == 1
+    lam = np.ascontiguousarray(lam.reshape(-1, lam.shape[-1]))
+    n, N = lam.shape[0], code.n_vars
+    row_ptr = np.asarray(code.row_ptr, dtype=np.int64)
+    col = np.asarray(code.col, dtype=np.int64)
+    slot = np.asarray(code.slot, dtype=np.int64)
+    alpha = float(code.alpha)
+    deg = np.diff(row_ptr)
+    ell = np.zeros((n, N))
+    use = slot >= 0
+    ell[:, use] = -lam[:, slot[use]]
+    # per layer: the edges of its checks as [checks][widest degree], the positions past a degree masked out
+    plan = []
+    for l in range(lp.size - 1):
+        cs = lc[lp[l]:lp[l + 1]]
+        pos = np.arange(int(deg[cs].max()))
+        real = pos[None, :] < deg[cs][:, None]
+        e = np.where(real, row_ptr[cs][:, None] + pos[None, :], 0)
+        plan.append((e, col[e], real, pos[None, None, :], e[real], col[e[real]]))
+    P = ell.copy()
+    R = np.zeros((n, col.size))
+    x = np.zeros((n, N), dtype=np.uint8)
+    its = np.zeros(n, dtype=np.int32)
+    act = np.arange(n)
+    with np.errstate(invalid="ignore"):
+        for _ in range(int(code.max_iter)):
+            if act.size == 0:
+                break
+            Pa, Ra = P[act], R[act]
+            P0 = Pa.copy() if _mutate == "stale" else None
+            for e, v, real, pos, er, vr in plan:
+                q = (Pa if P0 is None else P0)[:, v] - Ra[:, e]
+                a = np.where(real, np.abs(q), np.inf)
+                s = (q < 0) & real
+                i1 = a.argmin(axis=2)[:, :, None]              # the first of equal minima: the lowest position
+                m1 = np.take_along_axis(a, i1, axis=2)
+                np.put_along_axis(a, i1, np.inf, axis=2)
+                m2 = a.min(axis=2)[:, :, None]
+                sg = np.logical_xor.reduce(s, axis=2)[:, :, None]
+                r = alpha * np.where(pos == i1, m2, m1)
+                Rn = np.where(sg ^ s, -r, r)
+                if P0 is None:
+                    Pa[:, vr] = (q + Rn)[:, real]
+                else:
+                    Pa[:, vr] = Pa[:, vr] + (Rn[:, real] - Ra[:, er])
+                if _mutate != "no_store":
+                    Ra[:, er] = Rn[:, real]
+            xa = (Pa < 0).astype(np.uint8)
+            P[act], R[act], x[act] = Pa, Ra, xa
+            its[act] += 1
+            if code.early_stop:
+                act = act[ldpc_syndrome(xa, code).any(axis=1)]
+    return (x[0], its[0]) if single else (x, its)

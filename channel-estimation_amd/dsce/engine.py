@@ -32,6 +32,7 @@ EXPORTED = [
     "dsce_set_llr_scale_perf", "dsce_get_llr_scale_perf",
     "dsce_run_coded", "dsce_viterbi",
     "dsce_run_ldpc", "dsce_ldpc",
+    "dsce_run_ldpc_layered", "dsce_ldpc_layered",
 ]
 
 ABI_VERSION = 10
@@ -133,6 +134,10 @@ class LdpcDesc(C.Structure):
                 ("max_iter", C.c_int32), ("alpha", C.c_double), ("early_stop", C.c_int32)]
 
 
+class LdpcLayers(C.Structure):
+    _fields_ = [("n_layers", C.c_int32), ("layer_ptr", C.POINTER(C.c_int32)), ("layer_check", C.POINTER(C.c_int32))]
+
+
 class LdpcOut(C.Structure):
     _fields_ = [("bit_err", C.POINTER(C.c_int64)), ("frame_err", C.POINTER(C.c_int64)),
                 ("iter_sum", C.POINTER(C.c_int64))]
@@ -221,6 +226,10 @@ def load_library(path=None):
                                   C.POINTER(LdpcDesc), C.POINTER(LdpcOut)]
     lib.dsce_ldpc.argtypes = [vp, C.POINTER(LdpcDesc), C.c_int64, dp, C.c_int64, C.POINTER(C.c_uint8),
                               C.POINTER(C.c_int32)]
+    lib.dsce_run_ldpc_layered.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                          C.POINTER(LdpcDesc), C.POINTER(LdpcLayers), C.POINTER(LdpcOut)]
+    lib.dsce_ldpc_layered.argtypes = [vp, C.POINTER(LdpcDesc), C.POINTER(LdpcLayers), C.c_int64, dp, C.c_int64,
+                                      C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]
     for name in EXPORTED:
         fn = getattr(lib, name)
         if name != "dsce_last_error":
@@ -788,19 +797,35 @@ class Engine:
         return LdpcDesc(int(code.n_vars), int(code.n_checks), ptr[0], ptr[1], ptr[2], int(code.n_info),
                         int(code.max_iter), float(code.alpha), int(code.early_stop)), keep
 
-    def ldpc(self, lam, code):
+    @staticmethod
+    def _ldpc_layers(layers, code):
+        """(LdpcLayers, the int32 arrays it points to) of (layer_ptr, layer_check) (dsce.coding.make_layers)"""
+        keep = tuple(np.ascontiguousarray(np.asarray(a).reshape(-1), dtype=np.int32) for a in layers)
+        if len(keep) != 2 or keep[0].size < 1 or keep[1].size != int(code.n_checks):
+            raise ValueError("layers must be (layer_ptr [n_layers + 1], layer_check [n_checks])")
+        ptr = [a.ctypes.data_as(C.POINTER(C.c_int32)) for a in keep]
+        return LdpcLayers(keep[0].size - 1, ptr[0], ptr[1]), keep
+
+    def ldpc(self, lam, code, layers=None):
         """The engine's min-sum decoder on caller-supplied lam [n_cw][n_slots] (or
         [n_slots]; positive = the bit is 1) under `code` (dsce.coding.make_ldpc):
         (x uint8 [n_cw][n_vars], it int32 [n_cw]), the decided bits and the
         iterations performed (dsce_ldpc), equal to the bit to
-        dsce.coding.ldpc_decode.  Needs only the context."""
+        dsce.coding.ldpc_decode.  With layers = (layer_ptr, layer_check)
+        (dsce.coding.make_layers) the layered schedule (dsce_ldpc_layered), equal to
+        the bit to dsce.coding.ldpc_decode_layered.  Needs only the context."""
         lam, single = self._lam_rows(lam)
         desc, keep = self._ldpc_desc(code)
         x = np.zeros((lam.shape[0], int(code.n_vars)), dtype=np.uint8)
         it = np.zeros(lam.shape[0], dtype=np.int32)
-        self._chk(self.lib.dsce_ldpc(self.h, C.byref(desc), lam.shape[1], _dptr(lam), lam.shape[0],
-                                     x.ctypes.data_as(C.POINTER(C.c_uint8)), it.ctypes.data_as(C.POINTER(C.c_int32))),
-                  "dsce_ldpc")
+        xp, ip = x.ctypes.data_as(C.POINTER(C.c_uint8)), it.ctypes.data_as(C.POINTER(C.c_int32))
+        if layers is None:
+            self._chk(self.lib.dsce_ldpc(self.h, C.byref(desc), lam.shape[1], _dptr(lam), lam.shape[0], xp, ip),
+                      "dsce_ldpc")
+        else:
+            ly, keep_l = self._ldpc_layers(layers, code)
+            self._chk(self.lib.dsce_ldpc_layered(self.h, C.byref(desc), C.byref(ly), lam.shape[1], _dptr(lam),
+                                                 lam.shape[0], xp, ip), "dsce_ldpc_layered")
         return (x[0], it[0]) if single else (x, it)
 
     def ldpc_shapes(self, sid):
@@ -808,7 +833,7 @@ class Engine:
         d = self.scheme_dims(sid)
         return {f: (d.n_snr, d.n_iter + 1) for f in ("bit_err", "frame_err", "iter_sum")}
 
-    def run_ldpc(self, sid, seed, first_rep, n_rep, code, method="exact", out=None, branch="mmse"):
+    def run_ldpc(self, sid, seed, first_rep, n_rep, code, method="exact", out=None, branch="mmse", layers=None):
         """Decoded-error counts of the LDPC code `code` (dsce.coding.make_ldpc(ND m,
         rate)) over the LLRs that export_llr would return for realisations
         [first_rep, first_rep + n_rep) of scheme sid, one codeword per realisation,
@@ -820,13 +845,20 @@ class Engine:
         C-contiguous int64; only the given ones are computed) and `out` is
         returned; without it all are computed from zero.  BER = bit_err / (n_rep
         code.n_info), FER = frame_err / n_rep, mean iterations = iter_sum / n_rep.
-        branch 'perfect' (DSCE_LLR_PERFECT): the LLRs of the perfect-CSI branch."""
+        branch 'perfect' (DSCE_LLR_PERFECT): the LLRs of the perfect-CSI branch.
+        layers = (layer_ptr, layer_check) (dsce.coding.make_layers): the layered
+        schedule over that partition of the checks (dsce_run_ldpc_layered)."""
         shapes = self.ldpc_shapes(sid)
         o, out = self._acc_out(LdpcOut, shapes, np.int64, out, tuple(shapes), "ldpc")
         desc, keep = self._ldpc_desc(code)
-        self._chk(self.lib.dsce_run_ldpc(self.h, int(sid), int(seed), int(first_rep), int(n_rep),
-                                         self._llr_flag(method) | self._branch_flag(branch), C.byref(desc),
-                                         C.byref(o)), "dsce_run_ldpc")
+        flags = self._llr_flag(method) | self._branch_flag(branch)
+        if layers is None:
+            self._chk(self.lib.dsce_run_ldpc(self.h, int(sid), int(seed), int(first_rep), int(n_rep), flags,
+                                             C.byref(desc), C.byref(o)), "dsce_run_ldpc")
+        else:
+            ly, keep_l = self._ldpc_layers(layers, code)
+            self._chk(self.lib.dsce_run_ldpc_layered(self.h, int(sid), int(seed), int(first_rep), int(n_rep), flags,
+                                                     C.byref(desc), C.byref(ly), C.byref(o)), "dsce_run_ldpc_layered")
         return out
 
     # -- engine state ------------------------------------------------------------

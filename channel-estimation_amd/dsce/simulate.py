@@ -89,7 +89,12 @@ def main(argv=None):
                     help="with --ldpc: the min-sum normalisation, 0 < A <= 1")
     ap.add_argument("--ldpc-seed", type=int, default=7, metavar="S",
                     help="with --ldpc: the code is drawn from numpy.random.RandomState(S)")
+    ap.add_argument("--ldpc-schedule", choices=("flooding", "layered"), default=None,
+                    help="with --ldpc: flooding (the default; dsce_run_ldpc) or layered over the first-fit layers of "
+                         "dsce.coding.make_layers (dsce_run_ldpc_layered): the same error rate in fewer iterations")
     a = ap.parse_args(argv)
+    if a.ldpc_schedule and not a.ldpc:
+        raise SystemExit("--ldpc-schedule needs --ldpc")
     if (a.resume or a.stop_after is not None) and not a.checkpoint:
         raise SystemExit("--resume / --stop-after need --checkpoint")
     if a.calibrate and not a.rate:
@@ -186,7 +191,7 @@ def main(argv=None):
     codes, coded_s = [], 0.0
     # --ldpc: [scheme][branch: mmse, perfect][field: bit_err, frame_err, iter_sum][snr][stage]
     ldpc = np.zeros((len(names), 2, 3, nsnr, nst), dtype=np.int64)
-    ldpc_codes, ldpc_s = [], 0.0
+    ldpc_codes, ldpc_layers, ldpc_s = [], [], 0.0
     eng = None
     setup_s, t0 = 0.0, time.perf_counter()
     ck_path = None
@@ -289,17 +294,18 @@ def main(argv=None):
         coded_s = time.perf_counter() - t1
     if a.ldpc:
         # one dsce_run_ldpc pass per scheme and branch over the same realisations, after --coded
-        from dsce.coding import make_ldpc
+        from dsce.coding import make_layers, make_ldpc
         t1 = time.perf_counter()
         for i, s in enumerate(names):
             sc = S.schemes[s]
             ldpc_codes.append(make_ldpc(int(sc.n_data) * int(sc.bits_per_symbol), a.ldpc, seed=a.ldpc_seed,
                                         max_iter=a.ldpc_iters, alpha=a.ldpc_alpha))
+            ldpc_layers.append(make_layers(ldpc_codes[i]) if a.ldpc_schedule == "layered" else None)
             for b, branch in enumerate(("mmse", "perfect") if mine else ()):
                 out = {"bit_err": ldpc[i, b, 0], "frame_err": ldpc[i, b, 1], "iter_sum": ldpc[i, b, 2]}
                 for at in range(0, mine, step):
                     eng.run_ldpc(i, a.seed, first + at, min(step, mine - at), ldpc_codes[i], a.rate or "exact", out,
-                                 branch=branch)
+                                 branch=branch, layers=ldpc_layers[i])
         ldpc_s = time.perf_counter() - t1
     if eng is not None:
         eng.close()
@@ -417,7 +423,8 @@ def main(argv=None):
             extra["ldpc"][s] = {"rate": a.ldpc, "info_bits": int(c.n_info), "n_checks": int(c.n_checks),
                                 "max_iter": int(c.max_iter), "alpha": float(c.alpha), "seed": int(a.ldpc_seed),
                                 "four_cycles": int(c.four_cycles), "method": a.rate or "exact",
-                                "calibrated": bool(a.calibrate)}
+                                "calibrated": bool(a.calibrate), "schedule": a.ldpc_schedule or "flooding",
+                                "n_layers": ldpc_layers[i][0].size - 1 if ldpc_layers[i] else None}
             for b, branch in enumerate(("mmse", "perfect_ic")):
                 extra["ldpc"][s][branch] = {"ber": (ldpc[i, b, 0] / (float(reps) * c.n_info)).tolist(),
                                             "fer": (ldpc[i, b, 1] / float(reps)).tolist(),

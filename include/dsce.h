@@ -49,6 +49,9 @@
  *   dsce_run_ldpc         <- no counterpart in the script: the bit and frame errors and the
  *                            iterations of a normalised min-sum LDPC decoder on those LLRs
  *   dsce_ldpc             <- the same decoder on the caller's own decoder input
+ *   dsce_run_ldpc_layered <- dsce_run_ldpc with the layered schedule over a caller-given
+ *                            partition of the checks
+ *   dsce_ldpc_layered     <- the layered decoder on the caller's own decoder input
  *
  * Conventions
  *  - Return 0 on success, a negative DSCE_E* code on failure; the message is
@@ -108,6 +111,8 @@
  * the coded bit and frame errors of a K = 7 Viterbi decoder on the device.
  * DSCE_HAS_LDPC_RUN (still ABI 10) announces dsce_run_ldpc and dsce_ldpc: the
  * same counts from a normalised min-sum decoder of a caller-given LDPC code.
+ * DSCE_HAS_LDPC_LAYERED (still ABI 10) announces dsce_run_ldpc_layered and
+ * dsce_ldpc_layered: that decoder with the layered schedule.
  */
 #ifndef DSCE_H
 #define DSCE_H
@@ -886,8 +891,8 @@ int dsce_viterbi(dsce_ctx* ctx, const dsce_code_desc* code, int64_t n_slots, con
  *  rate 1/2, 30 KiB at rate 5/6).  The calls compare that on the host with the
  *  context's limit (option lds_max) and return DSCE_EINVAL naming the bytes and the
  *  limit when the code does not fit, before anything is launched.
- *  Not built: several small codewords per workgroup, a layered schedule, offset
- *  min-sum or sum-product, a device-memory fallback for codes beyond the LDS
+ *  Not built: several small codewords per workgroup, offset min-sum or
+ *  sum-product (a layered schedule: the section after this one), a device-memory fallback for codes beyond the LDS
  *  limit, a MEX command, both branches in one call, sharding over a multi-device
  *  handle. */
 #define DSCE_HAS_LDPC_RUN 1
@@ -939,6 +944,84 @@ int dsce_run_ldpc(dsce_ctx* ctx, int32_t scheme_id, uint64_t seed, uint64_t firs
  * 0, n_cw < 0 and a null lam or bits_out with n_cw > 0; n_cw = 0 does nothing. */
 int dsce_ldpc(dsce_ctx* ctx, const dsce_ldpc_desc* code, int64_t n_slots, const double* lam, int64_t n_cw,
               uint8_t* bits_out, int32_t* iters_out);
+
+/* ---- the same decoder with the layered schedule (DSCE_HAS_LDPC_LAYERED;
+ *      additive, ABI 10) ---------------------------------------------------- */
+/* Definitions.  Everything not mentioned is the section above: the code, slots,
+ * lam, the sign convention "positive ell = the bit is 0", the record (m1, i1, m2,
+ * sg, s_p), alpha, fp64 with no clipping, no renormalisation and no fused
+ * multiply-add, and the counts.
+ *  Layer partition: n_layers layers, the checks of layer l being
+ *  layer_check[layer_ptr[l] .. layer_ptr[l+1] - 1].  Every check appears in exactly
+ *  one layer, and no two checks of a layer share a variable: the checks of a layer
+ *  may then be processed in any order, or all at once, with the same bits, which
+ *  is what lets the device take a layer in parallel without atomics and the NumPy
+ *  twin (dsce/coding.py ldpc_decode_layered) be bit-identical.  One check per layer
+ *  (the serial schedule) is valid for every code; dsce/coding.py make_layers
+ *  builds a partition by first fit in check order.  The host checks the partition
+ *  in one walk over the edges.
+ *  Decoder (exactly this order):
+ *   1. ell_v as above; P_v = ell_v, and R_{c,p} = 0.0 for every edge.
+ *   2. One iteration runs the layers l = 0 .. n_layers - 1 in order.  For every
+ *      check c of layer l with variables v_0 .. v_{d-1}:
+ *        q_p = P_{v_p} - R_{c,p},  a_p = |q_p|,  s_p = (q_p < 0);
+ *        m1, i1 (the lowest p attaining the minimum), m2, sg, mu_p and r = alpha *
+ *        mu_p (one rounded product) exactly as in the flooding schedule;
+ *        R'_{c,p} = (sg ^ s_p) ? -r : r;
+ *        P_{v_p} = q_p + R'_{c,p} (one rounded sum), and R_{c,.} <- R'_{c,.}.
+ *      A check of a later layer reads the P that the earlier layers of the same
+ *      iteration have written.  After the last layer x_v = (P_v < 0) and it += 1;
+ *      if early_stop is set and every check's XOR of x is 0, stop.
+ *   3. After max_iter iterations at the latest the output is x of the last
+ *      iteration performed, and it.  A variable in no check keeps P_v = ell_v.
+ *  min is exact and "the lowest p among equal minima" is the lexicographic minimum
+ *  of (a_p, p), so a kernel may form the record by any reduction tree.
+ *  Why the all-zero codeword stays exact.  The check update is the flooding one,
+ *  and P <- q + R' commutes with the sign flip (1 - 2 c_v) as the variable sum did:
+ *  if every P_v and R_{c,p} before a check is multiplied by (1 - 2 c_v), then q_p is,
+ *  |q_p| is unchanged, sg is unchanged since the c of a check XOR to 0, R'_{c,p} is
+ *  multiplied by (1 - 2 c_{v_p}) and so is the new P_{v_p}, exactly.  The induction of
+ *  the section above carries over check by check, layer by layer: x becomes x ^ c,
+ *  the syndrome and the iteration count are unchanged.  The caveat on exact zeros
+ *  is the same.
+ *  Kernel: one workgroup per codeword, P and the check records in dynamic LDS, the
+ *  same 8 N + 24 M + 8 bytes, compared with lds_max in the same way.  Inside a layer
+ *  a lane is an edge: a check takes 2, 4, 8, 16 or 32 consecutive lanes of one wave
+ *  and its record is formed by a butterfly over them; a barrier separates the
+ *  layers, and with early_stop a read-only pass over the checks takes the syndrome
+ *  after the last layer.  The workgroup has as many lanes as the widest layer, 1024
+ *  at most; a wider layer is walked in strides.
+ *  Not built: offset min-sum or sum-product, several codewords per workgroup, a
+ *  device-memory fallback for codes beyond the LDS limit, a MEX command, both
+ *  branches in one call, sharding over a multi-device handle. */
+#define DSCE_HAS_LDPC_LAYERED 1
+typedef struct {
+    int32_t n_layers;             /* 1 .. n_checks */
+    const int32_t* layer_ptr;     /* [n_layers + 1], layer_ptr[0] = 0, strictly increasing, last = n_checks */
+    const int32_t* layer_check;   /* [n_checks]: the checks of layer l are layer_check[layer_ptr[l] .. layer_ptr[l+1]-1] */
+} dsce_ldpc_layers;
+
+/* dsce_run_ldpc with the decoder above: the same run in every respect (flags 0 |
+ * DSCE_LLR_MAXLOG | DSCE_LLR_PERFECT, the "k_llr" temporary, batches, SNR chunks,
+ * the export_stage_mb cut, padding realisations, n_rep = 0, counts ADDED into the
+ * caller's arrays, no change to the error counters, the MSE sums or
+ * dsce_path_info, member 0 on a multi-device handle); the decoder's name under
+ * dsce_enable_timing is "k_ldpc_layered".  DSCE_EINVAL, with a message naming the
+ * offender, nothing written and nothing launched: every refusal of dsce_run_ldpc;
+ * a null layers, layer_ptr or layer_check; n_layers outside 1 .. n_checks;
+ * layer_ptr[0] != 0, a layer without a check, layer_ptr[n_layers] != n_checks; a
+ * layer_check entry outside [0, n_checks); a check that appears twice (named); two
+ * checks of one layer that share a variable (the layer, both checks and the
+ * variable named). */
+int dsce_run_ldpc_layered(dsce_ctx* ctx, int32_t scheme_id, uint64_t seed, uint64_t first_rep, uint64_t n_rep,
+                          uint32_t flags, const dsce_ldpc_desc* code, const dsce_ldpc_layers* layers,
+                          const dsce_ldpc_out* out);
+
+/* dsce_ldpc with the decoder above: lam [n_cw][n_slots], bits_out [n_cw][n_vars],
+ * iters_out [n_cw] (optional).  Needs only a context.  DSCE_EINVAL as for dsce_ldpc
+ * and for the partition errors above; n_cw = 0 does nothing. */
+int dsce_ldpc_layered(dsce_ctx* ctx, const dsce_ldpc_desc* code, const dsce_ldpc_layers* layers, int64_t n_slots,
+                      const double* lam, int64_t n_cw, uint8_t* bits_out, int32_t* iters_out);
 
 /* ---- engine state ------------------------------------------------------- */
 int dsce_scheme_dims(dsce_ctx* ctx, int32_t scheme_id, dsce_dims* dims);

@@ -13,6 +13,16 @@ batch 8192), rates 1/2 and 3/4, 30 iterations, alpha 0.75, exact LLRs:
     flags).
 
     python tools/ldpc_measure.py --out profiles/ldpc_measure.json
+
+--schedule layered measures dsce_run_ldpc_layered (k_ldpc_layered) over the
+first-fit layers of dsce.coding.make_layers in the same way.  --schedule compare
+runs, per rate, flooding at the cap --iters, layered at that cap and layered at
+half of it (early stop on), one call of each per round so that the three
+alternate on the same device, `repeats` rounds after a warm-up round, and
+reports for each the kernel ms (best and every value), codewords per second,
+mean iterations, ns per codeword and iteration, and BER and FER per SNR point:
+
+    python tools/ldpc_measure.py --schedule compare --out profiles/ldpc_layered_measure.json
 """
 import argparse
 import json
@@ -23,6 +33,7 @@ import sys
 import tempfile
 import time
 
+import numpy as np
 import torch          # before the engine's library: one HIP runtime for both
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,18 +45,30 @@ FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=o
 
 
 def kernel_resources(vpt):
-    """.amdhsa_* of k_ldpc<vpt>"""
+    """.amdhsa_* of k_ldpc<vpt>, or of k_ldpc_layered for vpt = None"""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    unit = "kernels_ldpc.hip" if vpt is not None else "kernels_ldpc_layered.hip"
     with tempfile.TemporaryDirectory() as d:
         out = os.path.join(d, "k.s")
         subprocess.run([hipcc] + FLAGS + ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(PKG, "csrc"),
-                                          "--cuda-device-only", "-S", os.path.join(PKG, "csrc", "kernels_ldpc.hip"),
+                                          "--cuda-device-only", "-S", os.path.join(PKG, "csrc", unit),
                                           "-o", out], check=True, capture_output=True)
         txt = open(out).read()
-    m = re.search(r"\.amdhsa_kernel (\S*6k_ldpcILi%dE\S*)\n(.*?)\.end_amdhsa_kernel" % vpt, txt, re.S)
+    name = r"6k_ldpcILi%dE" % vpt if vpt is not None else "14k_ldpc_layeredE"
+    m = re.search(r"\.amdhsa_kernel (\S*%s\S*)\n(.*?)\.end_amdhsa_kernel" % name, txt, re.S)
     f = dict(re.findall(r"\.amdhsa_(\w+) (\S+)", m.group(2)))
     return {"kernel": m.group(1), "vgprs": int(f["next_free_vgpr"]), "sgprs": int(f["next_free_sgpr"]),
             "lds_static_bytes": int(f["group_segment_fixed_size"]), "scratch_bytes": int(f["private_segment_fixed_size"])}
+
+
+def layer_shape(code, layers):
+    """the lanes k_ldpc_layered gives each layer: a check takes the power of two >= its degree, a layer a multiple of 64"""
+    lp, lc = layers
+    deg = np.diff(code.row_ptr)
+    lanes = [-(-sum(max(2, 1 << int(d - 1).bit_length()) for d in deg[lc[lp[l]:lp[l + 1]]]) // 64) * 64
+             for l in range(lp.size - 1)]
+    return {"n_layers": int(lp.size - 1), "checks_per_layer": np.diff(lp).tolist(), "lanes_per_layer": lanes,
+            "threads_per_block_layered": min(1024, max(lanes))}
 
 
 def main(argv=None):
@@ -55,10 +78,11 @@ def main(argv=None):
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--alpha", type=float, default=0.75)
+    ap.add_argument("--schedule", choices=("flooding", "layered", "compare"), default="flooding")
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
 
-    from dsce.coding import make_code, make_ldpc
+    from dsce.coding import make_code, make_layers, make_ldpc
     from dsce.configs import build_setup
     from dsce.engine import build_engine, gpu_tx
     S = build_setup("default", schemes=("ofdm",), tx=gpu_tx(0))
@@ -70,7 +94,10 @@ def main(argv=None):
     res = {"config": "default", "scheme": "ofdm", "n_snr": nk, "snr_db": [float(x) for x in S.snr_db],
            "n_iter": int(S.n_iter), "slots": B, "reps": a.reps, "batch": a.batch,
            "device": torch.cuda.get_device_name(0), "repeats": a.repeats, "method": "exact", "codewords": ncw,
-           "max_iter": a.iters, "alpha": a.alpha, "lds_max": eng.get_option("lds_max"), "rates": {}}
+           "max_iter": a.iters, "alpha": a.alpha, "lds_max": eng.get_option("lds_max"), "schedule": a.schedule,
+           "rates": {}}
+    layered = a.schedule == "layered"
+    kname = "k_ldpc_layered" if layered else "k_ldpc"
 
     def timed(fn, names):
         eng.enable_timing(True)
@@ -82,16 +109,47 @@ def main(argv=None):
         eng.enable_timing(False)
         return {k: after[k][1] - before[k][1] for k in before}, w, out
 
-    for rate in ("1/2", "3/4"):
+    def entry(code, out, kd):
+        best = min(kd)
+        iters = float(out["iter_sum"].sum())
+        return {"max_iter": int(code.max_iter), "kernel_ms": kd, "kernel_ms_best": best,
+                "codewords_per_s": ncw / (best * 1e-3), "mean_iter": (out["iter_sum"] / float(a.reps)).tolist(),
+                "mean_iter_all": iters / ncw, "ns_per_codeword_iteration": best * 1e6 / iters,
+                "ber": (out["bit_err"] / (a.reps * float(code.n_info))).tolist(),
+                "fer": (out["frame_err"] / float(a.reps)).tolist()}
+
+    for rate in ("1/2", "3/4") if a.schedule == "compare" else ():
+        code = make_ldpc(B, rate, max_iter=a.iters, alpha=a.alpha)
+        layers = make_layers(code)
+        half = code._replace(max_iter=max(1, a.iters // 2))
+        runs = [("flooding", code, None, "k_ldpc"), ("layered", code, layers, "k_ldpc_layered"),
+                ("layered_half_cap", half, layers, "k_ldpc_layered")]
+        kd, outs = {k: [] for k, _, _, _ in runs}, {}
+        for rnd in range(a.repeats + 1):                     # round 0 warms up (buffers, clocks, code objects)
+            for key, c, ly, name in runs:
+                ms, w, outs[key] = timed(lambda: eng.run_ldpc(0, SEED, 0, a.reps, c, layers=ly), (name,))
+                if rnd:
+                    kd[key].append(ms[name])
+        r = {key: entry(c, outs[key], kd[key]) for key, c, ly, name in runs}
+        r.update({"info_bits": code.n_info, "n_checks": code.n_checks, "edges": int(code.col.size),
+                  "lds_dynamic_bytes_per_block": 8 * code.n_vars + 24 * code.n_checks + 8})
+        r.update(layer_shape(code, layers))
+        try:
+            r["k_ldpc_layered_resources"] = kernel_resources(None)
+        except Exception as e:
+            r["k_ldpc_layered_resources"] = {"error": str(e)[:200]}
+        res["rates"][rate] = r
+    for rate in ("1/2", "3/4") if a.schedule != "compare" else ():
         r = {}
         for early in (1, 0):
             code = make_ldpc(B, rate, max_iter=a.iters, alpha=a.alpha, early_stop=bool(early))
-            run = lambda: eng.run_ldpc(0, SEED, 0, a.reps, code)
+            layers = make_layers(code) if layered else None
+            run = lambda: eng.run_ldpc(0, SEED, 0, a.reps, code, layers=layers)
             run()                                            # warm-up (buffers, clocks, code objects)
             kd, kl, wall = [], [], []
             for _ in range(a.repeats):
-                ms, w, out = timed(run, ("k_ldpc", "k_llr"))
-                kd.append(ms["k_ldpc"])
+                ms, w, out = timed(run, (kname, "k_llr"))
+                kd.append(ms[kname])
                 kl.append(ms["k_llr"])
                 wall.append(w)
             best = min(kd)
@@ -112,7 +170,9 @@ def main(argv=None):
                   "four_cycles": code.four_cycles, "threads_per_block": nt, "variables_per_thread": vpt,
                   "lds_dynamic_bytes_per_block": 8 * code.n_vars + 24 * code.n_checks + 8})
         try:
-            r["k_ldpc_resources"] = kernel_resources(vpt)
+            r["k_ldpc_resources"] = kernel_resources(None if layered else vpt)
+            if layered:
+                r.update(layer_shape(code, layers))
         except Exception as e:                               # no compiler here: the run is still measured
             r["k_ldpc_resources"] = {"error": str(e)[:200]}
         conv = make_code(B, rate, interleaver=7)
