@@ -169,10 +169,11 @@ def frame_setup(name, scheme, sc, mod, SR, L, snr_db=SNR, n_iter=2, pdp="Vehicul
 
 
 @functools.lru_cache(maxsize=None)
-def geometry_setup(gid):
+def geometry_setup(gid, snr_db=SNR):
     """(T, S): GEOMETRIES[gid] and its oracle-format setup (one scheme, SNR
-    (15, 35) dB, 2 IC iterations, VehicularA at 500 km/h, 20 paths); S.name is
-    "geo:" + gid, unique per geometry (harness.oracle_mmse caches on it)."""
+    (15, 35) dB or the tuple snr_db, 2 IC iterations, VehicularA at 500 km/h, 20
+    paths); S.name is "geo:" + gid, unique per geometry (harness.oracle_mmse
+    caches on it and on the SNR points)."""
     T = GEOMETRIES[gid]
     SR = F * T.srm
     pm = pilot_matrix(T.L, T.K, T.pilots)
@@ -183,7 +184,7 @@ def geometry_setup(gid):
     else:
         mod = osu.FBMC(T.L, T.K, F, SR, 0, 8, 0)
         sc = fbmc_scheme(mod, pm, cons, osu.constellation(T.order, "PAM"), T.method)
-    return T, frame_setup("geo:" + gid, T.scheme, sc, mod, SR, T.L)
+    return T, frame_setup("geo:" + gid, T.scheme, sc, mod, SR, T.L, snr_db=snr_db)
 
 
 def dims(gid):

@@ -7,7 +7,9 @@ codeword on cycle-free codes and the codeword invariance with a separate encoder
 Then the header against the ctypes binding, the conventions pinned on the oracle's
 LLRs (ORACLE_LDPC_LAYERED), two deliberately wrong decoders that these must catch,
 and `python -m dsce.simulate --ldpc-schedule`.  No GPU call;
-tests/test_gpu_ldpc_layered.py compares the engine with the twin."""
+tests/test_gpu_ldpc_layered.py compares the engine with the twin and
+tests/test_gpu_ldpc_layered_ref.py runs the tree and invariance cases of this
+file through dsce_ldpc_layered."""
 import ctypes
 import os
 import re
