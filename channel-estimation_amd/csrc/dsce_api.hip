@@ -3268,7 +3268,9 @@ int dsce_viterbi(dsce_ctx* ctx, const dsce_code_desc* code, int64_t n_slots, con
 }
 
 // The checks of an LDPC description against n_slots slots and the context's LDS limit (dsce_run_ldpc, dsce_ldpc)
-static void check_ldpc(const dsce_ctx* ctx, const dsce_ldpc_desc* d, int64_t n_slots, const std::string& w) {
+// `lds` gives the bytes a code needs in the kernel `kname` that will decode it.
+static void check_ldpc(const dsce_ctx* ctx, const dsce_ldpc_desc* d, int64_t n_slots, const std::string& w,
+                       size_t (*lds)(int, int) = ldpc_lds_bytes, const char* kname = "k_ldpc") {
     if (!d || !d->row_ptr || !d->col || !d->slot) throw ApiError(DSCE_EINVAL, w + ": null code, row_ptr, col or slot");
     if (d->n_vars < 1) throw ApiError(DSCE_EINVAL, w + ": n_vars < 1");
     if (d->n_checks < 1) throw ApiError(DSCE_EINVAL, w + ": n_checks < 1");
@@ -3279,11 +3281,11 @@ static void check_ldpc(const dsce_ctx* ctx, const dsce_ldpc_desc* d, int64_t n_s
         throw ApiError(DSCE_EINVAL, w + ": alpha must be finite with 0 < alpha <= 1");
     if (d->early_stop != 0 && d->early_stop != 1) throw ApiError(DSCE_EINVAL, w + ": early_stop must be 0 or 1");
     // the limit first: it bounds N and M, so the table walks below are short
-    const size_t need = ldpc_lds_bytes(d->n_vars, d->n_checks);
+    const size_t need = lds(d->n_vars, d->n_checks);
     if (need > (size_t)ctx->op.lds_max)
         throw ApiError(DSCE_EINVAL, w + ": a code of " + std::to_string(d->n_vars) + " variables and " +
                                         std::to_string(d->n_checks) + " checks needs " + std::to_string(need) +
-                                        " bytes of LDS per workgroup (k_ldpc); the limit (lds_max) is " +
+                                        " bytes of LDS per workgroup (" + kname + "); the limit (lds_max) is " +
                                         std::to_string(ctx->op.lds_max));
     if (d->row_ptr[0] != 0) throw ApiError(DSCE_EINVAL, w + ": row_ptr[0] is not 0");
     for (int c = 0; c < d->n_checks; ++c) {
@@ -3502,6 +3504,108 @@ int dsce_ldpc_layered(dsce_ctx* ctx, const dsce_ldpc_desc* code, const dsce_ldpc
                           if (iters_out)
                               DSCE_HIP_CHECK(hipMemcpyAsync(iters_out, dit, (size_t)n_cw * sizeof(int), hipMemcpyDeviceToHost,
                                                             ctx->stream));
+                      };
+                  });
+    API_END
+}
+
+// The checks of the word lengths and the rule of the fixed-point decoder (dsce_run_ldpc_fixed, dsce_ldpc_fixed)
+static LdpcFixedParK check_ldpc_fixed(const dsce_ldpc_fixed_desc* fx, const std::string& w) {
+    if (!fx) throw ApiError(DSCE_EINVAL, w + ": null fx");
+    static_assert(ldpc_fixed_lds_bytes(2560, 1280) == (size_t)DSCE_LDPC_FIXED_LDS_BYTES(2560, 1280), "header and kernel LDS");
+    if (!(std::isfinite(fx->scale) && fx->scale > 0.0)) throw ApiError(DSCE_EINVAL, w + ": scale must be finite and > 0");
+    if (fx->q_ch < 2 || fx->q_ch > 16) throw ApiError(DSCE_EINVAL, w + ": q_ch outside 2 .. 16");
+    if (fx->q_msg < 2 || fx->q_msg > 16) throw ApiError(DSCE_EINVAL, w + ": q_msg outside 2 .. 16");
+    if (fx->q_app < std::max(fx->q_ch, fx->q_msg) || fx->q_app > 16)
+        throw ApiError(DSCE_EINVAL, w + ": q_app outside max(q_ch, q_msg) .. 16");
+    if (fx->alpha_shift < 0 || fx->alpha_shift > 8) throw ApiError(DSCE_EINVAL, w + ": alpha_shift outside 0 .. 8");
+    if (fx->alpha_num < 1 || fx->alpha_num > (1 << fx->alpha_shift))
+        throw ApiError(DSCE_EINVAL, w + ": alpha_num outside 1 .. 1 << alpha_shift");
+    if (fx->beta < 0 || fx->beta > 32767) throw ApiError(DSCE_EINVAL, w + ": beta outside 0 .. 32767");
+    LdpcFixedParK f{};
+    f.scale = fx->scale;
+    f.C = (1 << (fx->q_ch - 1)) - 1;
+    f.X = (1 << (fx->q_msg - 1)) - 1;
+    f.A = (1 << (fx->q_app - 1)) - 1;
+    f.an = fx->alpha_num;
+    f.sh = fx->alpha_shift;
+    f.half = (1 << fx->alpha_shift) >> 1;
+    f.beta = fx->beta;
+    return f;
+}
+
+// The caller's codeword against a checked description: entries 0 / 1, every check XORs to 0
+static void check_ldpc_codeword(const dsce_ldpc_desc* d, const uint8_t* word, const std::string& w) {
+    for (int v = 0; v < d->n_vars; ++v)
+        if (word[v] > 1) throw ApiError(DSCE_EINVAL, w + ": codeword entry " + std::to_string(v) + " is not 0 or 1");
+    for (int c = 0; c < d->n_checks; ++c) {
+        unsigned x = 0;
+        for (int e = d->row_ptr[c]; e < d->row_ptr[c + 1]; ++e) x ^= word[d->col[e]];
+        if (x) throw ApiError(DSCE_EINVAL, w + ": codeword does not satisfy check " + std::to_string(c));
+    }
+}
+
+// dsce_run_ldpc with the fixed-point decoder (DSCE_HAS_LDPC_FIXED): decoder_run with k_ldpc_fixed.
+int dsce_run_ldpc_fixed(dsce_ctx* ctx, int32_t id, uint64_t seed, uint64_t first_rep, uint64_t n_rep, uint32_t flags,
+                        const dsce_ldpc_desc* code, const dsce_ldpc_fixed_desc* fx, const uint8_t* codeword,
+                        const dsce_ldpc_out* out) {
+    TraceRange trace_range("dsce run ldpc fixed");
+    API_BEGIN
+    check_ctx(ctx);
+    Scheme& s = bulk_export_check(ctx, id, out, flags, DSCE_LLR_MAXLOG | DSCE_LLR_PERFECT, "dsce_run_ldpc_fixed");
+    check_ldpc(ctx, code, (int64_t)s.d.n_data * s.d.bits_per_symbol, "dsce_run_ldpc_fixed", ldpc_fixed_lds_bytes,
+               "k_ldpc_fixed");
+    LdpcFixedK q{};
+    q.f = check_ldpc_fixed(fx, "dsce_run_ldpc_fixed");
+    if (codeword) check_ldpc_codeword(code, codeword, "dsce_run_ldpc_fixed");
+    const size_t ncell = (size_t)ctx->nsnr * (ctx->niter + 1);
+    CountAcc acc{{out->bit_err, ncell}, {out->frame_err, ncell}, {out->iter_sum, ncell}};
+    decoder_run(ctx, s, id, seed, first_rep, n_rep, flags, "dsce_run_ldpc_fixed", acc, q.cw,
+                [&](DeviceTemps& tmp) {
+                    q.acc_iter = acc.dev(2);
+                    q.c = upload_ldpc(ctx, tmp, code);
+                    if (codeword) {
+                        uint8_t* dword = tmp.alloc<uint8_t>((size_t)code->n_vars);
+                        DSCE_HIP_CHECK(hipMemcpyAsync(dword, codeword, (size_t)code->n_vars, hipMemcpyHostToDevice,
+                                                      ctx->stream));
+                        DSCE_HIP_CHECK(hipStreamSynchronize(ctx->stream));      // the caller's array, not ours to hold
+                        q.word = dword;
+                    }
+                },
+                [&] {
+                    Timed t(ctx, "k_ldpc_fixed");
+                    launch_ldpc_fixed(ctx->stream, q);
+                });
+    API_END
+}
+
+// The decoder of dsce_run_ldpc_fixed on the caller's lam: k_ldpc_fixed_probe.
+int dsce_ldpc_fixed(dsce_ctx* ctx, const dsce_ldpc_desc* code, const dsce_ldpc_fixed_desc* fx, int64_t n_slots, const double* lam,
+                    int64_t n_cw, uint8_t* bits_out, int32_t* iters_out, int16_t* app_out) {
+    API_BEGIN
+    check_ctx(ctx);
+    LdpcFixedParK f{};
+    decoder_probe(ctx, "dsce_ldpc_fixed", n_slots, lam, n_cw, bits_out,
+                  [&] {
+                      check_ldpc(ctx, code, n_slots, "dsce_ldpc_fixed", ldpc_fixed_lds_bytes, "k_ldpc_fixed");
+                      f = check_ldpc_fixed(fx, "dsce_ldpc_fixed");
+                  },
+                  [&](DeviceTemps& tmp, const double* dlam) {
+                      const size_t N = (size_t)code->n_vars;
+                      const LdpcCodeK k = upload_ldpc(ctx, tmp, code);
+                      uint8_t* dbits = tmp.alloc<uint8_t>((size_t)n_cw * N);
+                      int* dit = tmp.alloc<int>((size_t)n_cw);
+                      short* dapp = app_out ? tmp.alloc<short>((size_t)n_cw * N) : nullptr;
+                      Timed t(ctx, "k_ldpc_fixed_probe");
+                      launch_ldpc_fixed_probe(ctx->stream, k, f, n_cw, n_slots, dlam, dbits, dit, dapp);
+                      return [=] {
+                          DSCE_HIP_CHECK(hipMemcpyAsync(bits_out, dbits, (size_t)n_cw * N, hipMemcpyDeviceToHost, ctx->stream));
+                          if (iters_out)
+                              DSCE_HIP_CHECK(hipMemcpyAsync(iters_out, dit, (size_t)n_cw * sizeof(int), hipMemcpyDeviceToHost,
+                                                            ctx->stream));
+                          if (app_out)
+                              DSCE_HIP_CHECK(hipMemcpyAsync(app_out, dapp, (size_t)n_cw * N * sizeof(short),
+                                                            hipMemcpyDeviceToHost, ctx->stream));
                       };
                   });
     API_END

@@ -523,6 +523,30 @@ void launch_ldpc_layered(hipStream_t s, const LdpcLayeredK& a);
 // (k_ldpc_layered_probe; dsce_ldpc_layered)
 void launch_ldpc_layered_probe(hipStream_t s, const LdpcCodeK& c, const LdpcLayersK& y, long long ncw, long long n_slots,
                                const double* lam, uint8_t* bits, int* iters);
+// The fixed-point decoder of include/dsce.h (DSCE_HAS_LDPC_FIXED; kernels_ldpc_fixed.hip): LdpcCodeK's tables (alpha
+// is not read) and the checked dsce_ldpc_fixed_desc as the integers the kernel uses.  Dynamic LDS per block: two flag
+// words, per check an 8-byte record (the two normalised minima as 16 bits each, the sign mask) and i1 | sg << 8 as 16
+// bits, then P [N] and ell [N] as int16: ldpc_fixed_lds_bytes, compared on the host with Opts::lds_max.
+struct LdpcFixedParK {
+    double scale;
+    int C, X, A;              // 2^(q - 1) - 1 of the channel, message and a-posteriori words
+    int an, sh, half, beta;   // r = max(((mu an + half) >> sh) - beta, 0), half = (1 << sh) >> 1
+};
+constexpr inline size_t ldpc_fixed_lds_bytes(int N, int M) { return (size_t)N * 4 + (size_t)M * 10 + 8; }
+// k_ldpc_fixed after k_llr (dsce_run_ldpc_fixed): one block per codeword of cw; `word` [N] is the caller's codeword
+// (0 / 1, checked by the host) or null for the all-zero word.
+struct LdpcFixedK {
+    LdpcCodeK c;
+    LdpcFixedParK f;
+    CodewordK cw;
+    const uint8_t* word;             // [N], or null
+    unsigned long long* acc_iter;    // [nsnr][S], or null
+};
+void launch_ldpc_fixed(hipStream_t s, const LdpcFixedK& a);
+// the same decoder on lam [ncw][n_slots]: x to bits [ncw][N], the iterations performed to iters [ncw] (or null), the
+// final P to app [ncw][N] (or null) (k_ldpc_fixed_probe; dsce_ldpc_fixed)
+void launch_ldpc_fixed_probe(hipStream_t s, const LdpcCodeK& c, const LdpcFixedParK& f, long long ncw, long long n_slots,
+                             const double* lam, uint8_t* bits, int* iters, short* app);
 // LLRs of n points x (pn: one value or one per point), out [n][m]
 void launch_llr_probe(hipStream_t s, const LlrTab& t, const double2* x, const double* pn, long long n_pn, long long n,
                       bool maxlog, double* out);

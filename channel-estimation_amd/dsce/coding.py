@@ -540,3 +540,184 @@ def ldpc_decode_layered(lam, code, layers, _mutate=None):
             if code.early_stop:
                 act = act[ldpc_syndrome(xa, code).any(axis=1)]
     return (x[0], its[0]) if single else (x, its)
+
+
+# ---- the flooding decoder in fixed point (include/dsce.h, DSCE_HAS_LDPC_FIXED) ----
+
+LdpcFixed = collections.namedtuple("LdpcFixed", "scale q_ch q_msg q_app alpha_num alpha_shift beta")
+LdpcFixed.__doc__ = """The word lengths and the rule of dsce_run_ldpc_fixed / dsce_ldpc_fixed (dsce_ldpc_fixed_desc of
+include/dsce.h): scale quantiser steps per LLR unit; q_ch, q_msg, q_app bits of the channel,
+message and a-posteriori words (symmetric ranges +-(2^(q-1) - 1)); the normalisation
+alpha_num / 2^alpha_shift, rounded half up; the offset beta."""
+
+
+def make_fixed(q_ch=6, q_msg=6, q_app=8, scale=2.0, alpha_num=1, alpha_shift=0, beta=1):
+    """An LdpcFixed, checked (check_fixed).  The defaults: 6 / 6 / 8 bit, two steps per LLR
+    unit (a channel clip of 15.5), no normalisation, offset 1."""
+    fx = LdpcFixed(float(scale), int(q_ch), int(q_msg), int(q_app), int(alpha_num), int(alpha_shift), int(beta))
+    check_fixed(fx)
+    return fx
+
+
+def check_fixed(fx):
+    """The host's checks of a dsce_ldpc_fixed_desc, in its order and with its words: ValueError
+    naming the offender.  Returns (C, X, A)."""
+    if fx is None:
+        raise ValueError("null fx")
+    if not (np.isfinite(fx.scale) and fx.scale > 0.0):
+        raise ValueError("scale must be finite and > 0")
+    if not 2 <= fx.q_ch <= 16:
+        raise ValueError("q_ch outside 2 .. 16")
+    if not 2 <= fx.q_msg <= 16:
+        raise ValueError("q_msg outside 2 .. 16")
+    if not max(fx.q_ch, fx.q_msg) <= fx.q_app <= 16:
+        raise ValueError("q_app outside max(q_ch, q_msg) .. 16")
+    if not 0 <= fx.alpha_shift <= 8:
+        raise ValueError("alpha_shift outside 0 .. 8")
+    if not 1 <= fx.alpha_num <= (1 << fx.alpha_shift):
+        raise ValueError("alpha_num outside 1 .. 1 << alpha_shift")
+    if not 0 <= fx.beta <= 32767:
+        raise ValueError("beta outside 0 .. 32767")
+    return tuple((1 << (q - 1)) - 1 for q in (fx.q_ch, fx.q_msg, fx.q_app))
+
+
+def check_codeword(code, codeword):
+    """The host's checks of the codeword of dsce_run_ldpc_fixed: ValueError naming the first
+    entry that is not 0 or 1, or the first unsatisfied check.  Returns it as uint8 [n_vars]."""
+    c = np.ascontiguousarray(np.asarray(codeword).reshape(-1), dtype=np.uint8)
+    if c.size != int(code.n_vars):
+        raise ValueError("codeword must have n_vars entries")
+    if (c > 1).any():
+        raise ValueError("codeword entry %d is not 0 or 1" % int(np.flatnonzero(c > 1)[0]))
+    syn = ldpc_syndrome(c, code)
+    if syn.any():
+        raise ValueError("codeword does not satisfy check %d" % int(np.flatnonzero(syn)[0]))
+    return c
+
+
+def ldpc_fixed_lds_bytes(n_vars, n_checks):
+    """Dynamic LDS bytes of k_ldpc_fixed per workgroup (DSCE_LDPC_FIXED_LDS_BYTES)."""
+    return 4 * int(n_vars) + 10 * int(n_checks) + 8
+
+
+def ldpc_quantise(lam, fx):
+    """Step 1 of the fixed-point decoder on lam (any shape): int32 ell = Q(-lam): t = (-lam) *
+    scale, magnitude min(floor(|t| + 0.5), C), the sign of t; NaN gives 0, +-inf saturates."""
+    C = check_fixed(fx)[0]
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = (-np.asarray(lam, dtype=np.float64)) * np.float64(fx.scale)
+        a = np.abs(t)
+        sat = a >= C                                          # False for NaN
+        mag = np.where(sat, float(C), np.floor(np.where(sat | np.isnan(a), 0.0, a) + 0.5))
+    mag = mag.astype(np.int32)
+    return np.where(t < 0, -mag, mag).astype(np.int32)
+
+
+def ldpc_decode_fixed(lam, code, fx, _mutate=None, _ell=None):
+    """Fixed-point min-sum decoding of lam [n_cw][n_slots] (or [n_slots]; positive = the bit
+    is 1) under `code` and the LdpcFixed `fx`: (x uint8 [n_cw][n_vars], it int32 [n_cw], P
+    int16 [n_cw][n_vars]), the decided bits and the a-posteriori sums of the last iteration
+    performed and the number of iterations.  The twin of k_ldpc_fixed, in the integers of
+    include/dsce.h: ell = ldpc_quantise (0 for slot -1), P = ell, R = 0; per check q_p =
+    clamp(P_v - R_p, +-X), the record of ldpc_decode on |q_p| and q_p < 0, r = max(((mu *
+    alpha_num + half) >> alpha_shift) - beta, 0), R'_p = +-r; per variable P' = clamp(ell +
+    sum R', +-A); x = P' < 0; with early_stop a codeword stops once H x = 0.  code.alpha is
+    not read.  _ell (int [n_cw][n_vars]) replaces the quantiser's output (ldpc_counts_fixed).
+    _mutate is for the tests only: 'trunc' (no rounding term), 'late_clamp' (q_p not
+    clamped), 'beta_first' (the offset before the normalisation)."""
+    C, X, A = check_fixed(fx)
+    an, sh, beta = int(fx.alpha_num), int(fx.alpha_shift), int(fx.beta)
+    half = 0 if _mutate == "trunc" else (1 << sh) >> 1
+    N, M = code.n_vars, code.n_checks
+    row_ptr = np.asarray(code.row_ptr, dtype=np.int64)
+    col = np.asarray(code.col, dtype=np.int64)
+    slot = np.asarray(code.slot, dtype=np.int64)
+    if _ell is None:
+        lam = np.asarray(lam, dtype=np.float64)
+        single = lam.ndim == 1
+        lam = lam.reshape(-1, lam.shape[-1])
+        ell = np.zeros((lam.shape[0], N), dtype=np.int32)
+        use = slot >= 0
+        ell[:, use] = ldpc_quantise(lam[:, slot[use]], fx)
+    else:
+        ell = np.asarray(_ell, dtype=np.int32)
+        single = ell.ndim == 1
+        ell = ell.reshape(-1, N)
+    n = ell.shape[0]
+    deg = np.diff(row_ptr)
+    E = col.size
+    chk = np.repeat(np.arange(M), deg)
+    pos = np.arange(E) - row_ptr[chk]
+    by_var = np.argsort(col, kind="stable")                 # the edges grouped by variable
+    vptr = np.concatenate([[0], np.cumsum(np.bincount(col, minlength=N))])
+    big = np.int32(0x7FFFFFFF)
+    P = ell.copy()
+    R = np.zeros((n, E), dtype=np.int32)
+    x = np.zeros((n, N), dtype=np.uint8)
+    its = np.zeros(n, dtype=np.int32)
+    act = np.arange(n)
+    for _ in range(int(code.max_iter)):
+        if act.size == 0:
+            break
+        Pa, Ra = P[act], R[act]
+        na = act.size
+        m1 = np.full((na, M), big, dtype=np.int32)
+        m2 = np.full((na, M), big, dtype=np.int32)
+        i1 = np.zeros((na, M), dtype=np.int64)
+        sg = np.zeros((na, M), dtype=bool)
+        sgn = np.zeros((na, E), dtype=bool)
+        for p in range(int(deg.max())):
+            cs = np.flatnonzero(deg > p)
+            e = row_ptr[cs] + p
+            q = Pa[:, col[e]] - Ra[:, e]
+            if _mutate != "late_clamp":
+                q = np.clip(q, -X, X)
+            a = np.abs(q)
+            s = q < 0
+            sgn[:, e] = s
+            c1, c2 = m1[:, cs], m2[:, cs]
+            lt1 = a < c1
+            lt2 = ~lt1 & (a < c2)
+            m2[:, cs] = np.where(lt1, c1, np.where(lt2, a, c2))
+            m1[:, cs] = np.where(lt1, a, c1)
+            i1[:, cs] = np.where(lt1, p, i1[:, cs])
+            sg[:, cs] ^= s
+        mu = np.where(pos[None, :] == i1[:, chk], m2[:, chk], m1[:, chk]).astype(np.int64)
+        if _mutate == "beta_first":
+            r = (np.maximum(mu - beta, 0) * an + half) >> sh
+        else:
+            r = np.maximum(((mu * an + half) >> sh) - beta, 0)
+        r = r.astype(np.int32)
+        Rn = np.where(sg[:, chk] ^ sgn, -r, r)
+        run = np.concatenate([np.zeros((na, 1), dtype=np.int64), np.cumsum(Rn[:, by_var], axis=1, dtype=np.int64)], axis=1)
+        acc = np.clip(ell[act] + (run[:, vptr[1:]] - run[:, vptr[:-1]]), -A, A).astype(np.int32)
+        xa = (acc < 0).astype(np.uint8)
+        P[act], R[act], x[act] = acc, Rn, xa
+        its[act] += 1
+        if code.early_stop:
+            act = act[ldpc_syndrome(xa, code).any(axis=1)]
+    P = P.astype(np.int16)
+    return (x[0], its[0], P[0]) if single else (x, its, P)
+
+
+def ldpc_counts_fixed(llr, sym, code, fx, codeword=None):
+    """The definition of dsce_run_ldpc_fixed on exported arrays: llr [n][n_snr][S][ND][m]
+    (export_llr) and sym [n][ND] (export) -> dict(bit_err, frame_err, iter_sum), int64
+    [n_snr][S].  lam as in coded_counts, quantised (ldpc_quantise), negated where the
+    codeword (uint8 [n_vars], checked; None = all zero) has a 1; ldpc_decode_fixed decodes,
+    and the decided information bits that differ from the codeword are counted."""
+    llr = np.asarray(llr, dtype=np.float64)
+    n, nk, S, nd, m = llr.shape
+    t = ((np.asarray(sym)[..., None] >> np.arange(m)) & 1).astype(bool).reshape(n, 1, 1, nd * m)
+    flat = llr.reshape(n, nk, S, nd * m)
+    lam = np.where(t, -flat, flat).reshape(n * nk * S, nd * m)
+    c = np.zeros(int(code.n_vars), dtype=np.uint8) if codeword is None else check_codeword(code, codeword)
+    slot = np.asarray(code.slot, dtype=np.int64)
+    ell = np.zeros((lam.shape[0], int(code.n_vars)), dtype=np.int32)
+    use = slot >= 0
+    ell[:, use] = ldpc_quantise(lam[:, slot[use]], fx)
+    ell = np.where(c[None, :].astype(bool), -ell, ell)
+    x, it, P = ldpc_decode_fixed(None, code, fx, _ell=ell)
+    bit = (x ^ c[None, :])[:, :code.n_info].astype(np.int64).sum(axis=1)
+    return dict(bit_err=bit.reshape(n, nk, S).sum(axis=0), frame_err=(bit > 0).astype(np.int64).reshape(n, nk, S).sum(axis=0),
+                iter_sum=it.astype(np.int64).reshape(n, nk, S).sum(axis=0))

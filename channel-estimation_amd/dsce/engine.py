@@ -33,6 +33,7 @@ EXPORTED = [
     "dsce_run_coded", "dsce_viterbi",
     "dsce_run_ldpc", "dsce_ldpc",
     "dsce_run_ldpc_layered", "dsce_ldpc_layered",
+    "dsce_run_ldpc_fixed", "dsce_ldpc_fixed",
 ]
 
 ABI_VERSION = 10
@@ -138,6 +139,11 @@ class LdpcLayers(C.Structure):
     _fields_ = [("n_layers", C.c_int32), ("layer_ptr", C.POINTER(C.c_int32)), ("layer_check", C.POINTER(C.c_int32))]
 
 
+class LdpcFixedDesc(C.Structure):
+    _fields_ = [("scale", C.c_double), ("q_ch", C.c_int32), ("q_msg", C.c_int32), ("q_app", C.c_int32),
+                ("alpha_num", C.c_int32), ("alpha_shift", C.c_int32), ("beta", C.c_int32)]
+
+
 class LdpcOut(C.Structure):
     _fields_ = [("bit_err", C.POINTER(C.c_int64)), ("frame_err", C.POINTER(C.c_int64)),
                 ("iter_sum", C.POINTER(C.c_int64))]
@@ -230,6 +236,11 @@ def load_library(path=None):
                                           C.POINTER(LdpcDesc), C.POINTER(LdpcLayers), C.POINTER(LdpcOut)]
     lib.dsce_ldpc_layered.argtypes = [vp, C.POINTER(LdpcDesc), C.POINTER(LdpcLayers), C.c_int64, dp, C.c_int64,
                                       C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]
+    lib.dsce_run_ldpc_fixed.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                        C.POINTER(LdpcDesc), C.POINTER(LdpcFixedDesc), C.POINTER(C.c_uint8),
+                                        C.POINTER(LdpcOut)]
+    lib.dsce_ldpc_fixed.argtypes = [vp, C.POINTER(LdpcDesc), C.POINTER(LdpcFixedDesc), C.c_int64, dp, C.c_int64,
+                                    C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_int16)]
     for name in EXPORTED:
         fn = getattr(lib, name)
         if name != "dsce_last_error":
@@ -806,19 +817,36 @@ class Engine:
         ptr = [a.ctypes.data_as(C.POINTER(C.c_int32)) for a in keep]
         return LdpcLayers(keep[0].size - 1, ptr[0], ptr[1]), keep
 
-    def ldpc(self, lam, code, layers=None):
+    @staticmethod
+    def _ldpc_fixed(fx):
+        """LdpcFixedDesc of a dsce.coding.LdpcFixed"""
+        return LdpcFixedDesc(float(fx.scale), int(fx.q_ch), int(fx.q_msg), int(fx.q_app), int(fx.alpha_num),
+                             int(fx.alpha_shift), int(fx.beta))
+
+    def ldpc(self, lam, code, layers=None, fixed=None):
         """The engine's min-sum decoder on caller-supplied lam [n_cw][n_slots] (or
         [n_slots]; positive = the bit is 1) under `code` (dsce.coding.make_ldpc):
         (x uint8 [n_cw][n_vars], it int32 [n_cw]), the decided bits and the
         iterations performed (dsce_ldpc), equal to the bit to
         dsce.coding.ldpc_decode.  With layers = (layer_ptr, layer_check)
         (dsce.coding.make_layers) the layered schedule (dsce_ldpc_layered), equal to
-        the bit to dsce.coding.ldpc_decode_layered.  Needs only the context."""
+        the bit to dsce.coding.ldpc_decode_layered.  With fixed = an LdpcFixed
+        (dsce.coding.make_fixed) the fixed-point decoder (dsce_ldpc_fixed), equal to
+        dsce.coding.ldpc_decode_fixed, and a third result: app int16 [n_cw][n_vars],
+        the final a-posteriori sums.  Needs only the context."""
+        if fixed is not None and layers is not None:
+            raise ValueError("fixed and layers exclude each other: the fixed-point decoder has the flooding schedule")
         lam, single = self._lam_rows(lam)
         desc, keep = self._ldpc_desc(code)
         x = np.zeros((lam.shape[0], int(code.n_vars)), dtype=np.uint8)
         it = np.zeros(lam.shape[0], dtype=np.int32)
         xp, ip = x.ctypes.data_as(C.POINTER(C.c_uint8)), it.ctypes.data_as(C.POINTER(C.c_int32))
+        if fixed is not None:
+            app = np.zeros(x.shape, dtype=np.int16)
+            fd = self._ldpc_fixed(fixed)
+            self._chk(self.lib.dsce_ldpc_fixed(self.h, C.byref(desc), C.byref(fd), lam.shape[1], _dptr(lam), lam.shape[0],
+                                               xp, ip, app.ctypes.data_as(C.POINTER(C.c_int16))), "dsce_ldpc_fixed")
+            return (x[0], it[0], app[0]) if single else (x, it, app)
         if layers is None:
             self._chk(self.lib.dsce_ldpc(self.h, C.byref(desc), lam.shape[1], _dptr(lam), lam.shape[0], xp, ip),
                       "dsce_ldpc")
@@ -833,7 +861,8 @@ class Engine:
         d = self.scheme_dims(sid)
         return {f: (d.n_snr, d.n_iter + 1) for f in ("bit_err", "frame_err", "iter_sum")}
 
-    def run_ldpc(self, sid, seed, first_rep, n_rep, code, method="exact", out=None, branch="mmse", layers=None):
+    def run_ldpc(self, sid, seed, first_rep, n_rep, code, method="exact", out=None, branch="mmse", layers=None,
+                 fixed=None, codeword=None):
         """Decoded-error counts of the LDPC code `code` (dsce.coding.make_ldpc(ND m,
         rate)) over the LLRs that export_llr would return for realisations
         [first_rep, first_rep + n_rep) of scheme sid, one codeword per realisation,
@@ -847,11 +876,31 @@ class Engine:
         code.n_info), FER = frame_err / n_rep, mean iterations = iter_sum / n_rep.
         branch 'perfect' (DSCE_LLR_PERFECT): the LLRs of the perfect-CSI branch.
         layers = (layer_ptr, layer_check) (dsce.coding.make_layers): the layered
-        schedule over that partition of the checks (dsce_run_ldpc_layered)."""
+        schedule over that partition of the checks (dsce_run_ldpc_layered).
+        fixed = an LdpcFixed (dsce.coding.make_fixed): the fixed-point decoder
+        (dsce_run_ldpc_fixed), with codeword = a word of the code (uint8 [n_vars],
+        dsce.coding.ldpc_encode) transmitted in place of the all-zero word, which
+        in integers is optimistic at ties (include/dsce.h); bit_err then counts the
+        decided information bits that differ from it."""
+        if fixed is not None and layers is not None:
+            raise ValueError("fixed and layers exclude each other: the fixed-point decoder has the flooding schedule")
+        if codeword is not None and fixed is None:
+            raise ValueError("codeword needs fixed: the fp64 decoders simulate the all-zero word, which is exact for them")
         shapes = self.ldpc_shapes(sid)
         o, out = self._acc_out(LdpcOut, shapes, np.int64, out, tuple(shapes), "ldpc")
         desc, keep = self._ldpc_desc(code)
         flags = self._llr_flag(method) | self._branch_flag(branch)
+        if fixed is not None:
+            fd = self._ldpc_fixed(fixed)
+            word = None
+            if codeword is not None:
+                word = np.ascontiguousarray(np.asarray(codeword).reshape(-1), dtype=np.uint8)
+                if word.size != int(code.n_vars):
+                    raise ValueError("codeword must have n_vars entries")
+            wp = None if word is None else word.ctypes.data_as(C.POINTER(C.c_uint8))
+            self._chk(self.lib.dsce_run_ldpc_fixed(self.h, int(sid), int(seed), int(first_rep), int(n_rep), flags,
+                                                   C.byref(desc), C.byref(fd), wp, C.byref(o)), "dsce_run_ldpc_fixed")
+            return out
         if layers is None:
             self._chk(self.lib.dsce_run_ldpc(self.h, int(sid), int(seed), int(first_rep), int(n_rep), flags,
                                              C.byref(desc), C.byref(o)), "dsce_run_ldpc")

@@ -92,9 +92,41 @@ def main(argv=None):
     ap.add_argument("--ldpc-schedule", choices=("flooding", "layered"), default=None,
                     help="with --ldpc: flooding (the default; dsce_run_ldpc) or layered over the first-fit layers of "
                          "dsce.coding.make_layers (dsce_run_ldpc_layered): the same error rate in fewer iterations")
+    ap.add_argument("--ldpc-fixed", default=None, metavar="QCH,QMSG,QAPP",
+                    help="with --ldpc: also decode in fixed point (dsce_run_ldpc_fixed) with these word lengths in bits "
+                         "of the channel values, the messages and the a-posteriori sums, a real codeword drawn from "
+                         "--ldpc-seed (dsce.coding.ldpc_encode); results under ldpc[scheme]['fixed'] beside the fp64 ones")
+    ap.add_argument("--ldpc-scale", type=float, default=None, metavar="S",
+                    help="with --ldpc-fixed (required): quantiser steps per LLR unit; the channel clip is "
+                         "(2^(QCH-1) - 1) / S")
+    ap.add_argument("--ldpc-offset", type=int, default=1, metavar="B", help="with --ldpc-fixed: the offset beta (default 1)")
+    ap.add_argument("--ldpc-alpha-q", default="1/2^0", metavar="NUM/2^SH",
+                    help="with --ldpc-fixed: the normalisation NUM / 2^SH, rounded half up (default 1/2^0: none)")
     a = ap.parse_args(argv)
     if a.ldpc_schedule and not a.ldpc:
         raise SystemExit("--ldpc-schedule needs --ldpc")
+    ldpc_fx = None
+    if a.ldpc_fixed is not None or a.ldpc_scale is not None:
+        if not a.ldpc:
+            raise SystemExit("--ldpc-fixed / --ldpc-scale need --ldpc")
+        if a.ldpc_fixed is None or a.ldpc_scale is None:
+            raise SystemExit("--ldpc-fixed and --ldpc-scale go together")
+        if a.ldpc_schedule == "layered":
+            raise SystemExit("--ldpc-fixed cannot be combined with --ldpc-schedule layered (the fixed-point decoder has "
+                             "the flooding schedule)")
+        import re
+        words = re.fullmatch(r"(\d+),(\d+),(\d+)", a.ldpc_fixed.strip())
+        if not words:
+            raise SystemExit("--ldpc-fixed takes three word lengths, QCH,QMSG,QAPP")
+        alpha_q = re.fullmatch(r"(\d+)/2\^(\d+)", a.ldpc_alpha_q.strip())
+        if not alpha_q:
+            raise SystemExit("--ldpc-alpha-q takes NUM/2^SH, for instance 3/2^2")
+        from dsce.coding import make_fixed
+        try:
+            ldpc_fx = make_fixed(*[int(x) for x in words.groups()], scale=a.ldpc_scale, alpha_num=int(alpha_q.group(1)),
+                                 alpha_shift=int(alpha_q.group(2)), beta=a.ldpc_offset)
+        except ValueError as e:
+            raise SystemExit("--ldpc-fixed: %s" % e)
     if (a.resume or a.stop_after is not None) and not a.checkpoint:
         raise SystemExit("--resume / --stop-after need --checkpoint")
     if a.calibrate and not a.rate:
@@ -192,6 +224,7 @@ def main(argv=None):
     # --ldpc: [scheme][branch: mmse, perfect][field: bit_err, frame_err, iter_sum][snr][stage]
     ldpc = np.zeros((len(names), 2, 3, nsnr, nst), dtype=np.int64)
     ldpc_codes, ldpc_layers, ldpc_s = [], [], 0.0
+    ldpcf = np.zeros_like(ldpc)                                # the same from dsce_run_ldpc_fixed (--ldpc-fixed)
     eng = None
     setup_s, t0 = 0.0, time.perf_counter()
     ck_path = None
@@ -306,6 +339,15 @@ def main(argv=None):
                 for at in range(0, mine, step):
                     eng.run_ldpc(i, a.seed, first + at, min(step, mine - at), ldpc_codes[i], a.rate or "exact", out,
                                  branch=branch, layers=ldpc_layers[i])
+            if ldpc_fx is not None:
+                # the transmitted word: information bits from the frozen stream of --ldpc-seed
+                from dsce.coding import ldpc_encode
+                word = ldpc_encode(np.random.RandomState(a.ldpc_seed).randint(0, 2, ldpc_codes[i].n_info), ldpc_codes[i])
+                for b, branch in enumerate(("mmse", "perfect") if mine else ()):
+                    out = {"bit_err": ldpcf[i, b, 0], "frame_err": ldpcf[i, b, 1], "iter_sum": ldpcf[i, b, 2]}
+                    for at in range(0, mine, step):
+                        eng.run_ldpc(i, a.seed, first + at, min(step, mine - at), ldpc_codes[i], a.rate or "exact", out,
+                                     branch=branch, fixed=ldpc_fx, codeword=word)
         ldpc_s = time.perf_counter() - t1
     if eng is not None:
         eng.close()
@@ -352,6 +394,8 @@ def main(argv=None):
             coded = allreduce_counts(coded, dev)
         if a.ldpc:
             ldpc = allreduce_counts(ldpc, dev)
+            if ldpc_fx is not None:
+                ldpcf = allreduce_counts(ldpcf, dev)
         if a.calibrate:
             closs_e = allreduce_counts(closs_e, dev)
             closs_p = allreduce_counts(closs_p, dev)
@@ -429,6 +473,14 @@ def main(argv=None):
                 extra["ldpc"][s][branch] = {"ber": (ldpc[i, b, 0] / (float(reps) * c.n_info)).tolist(),
                                             "fer": (ldpc[i, b, 1] / float(reps)).tolist(),
                                             "mean_iter": (ldpc[i, b, 2] / float(reps)).tolist()}
+            if ldpc_fx is not None:
+                C = (1 << (ldpc_fx.q_ch - 1)) - 1
+                extra["ldpc"][s]["fixed"] = dict(ldpc_fx._asdict(), clip=C / ldpc_fx.scale, codeword="ldpc_encode of "
+                                                 "RandomState(seed).randint(0, 2, info_bits)")
+                for b, branch in enumerate(("mmse", "perfect_ic")):
+                    extra["ldpc"][s]["fixed"][branch] = {"ber": (ldpcf[i, b, 0] / (float(reps) * c.n_info)).tolist(),
+                                                         "fer": (ldpcf[i, b, 1] / float(reps)).tolist(),
+                                                         "mean_iter": (ldpcf[i, b, 2] / float(reps)).tolist()}
     extra["realisations_per_s"] = reps / extra["seconds"]
     res = results.make(S, names, counts, bits, reps, a.seed, extra=extra)
     if rank != 0:

@@ -23,6 +23,20 @@ reports for each the kernel ms (best and every value), codewords per second,
 mean iterations, ns per codeword and iteration, and BER and FER per SNR point:
 
     python tools/ldpc_measure.py --schedule compare --out profiles/ldpc_layered_measure.json
+
+--fixed measures dsce_run_ldpc_fixed (k_ldpc_fixed) against dsce_run_ldpc (k_ldpc)
+at the same shape: per rate, the fp64 flooding decoder (alpha --alpha) and the
+fixed-point one (6 / 6 / 8 bit, scale 2, offset 1; then alpha 3/4 rounded, offset
+0) with a real codeword, early stop on, then both without early stop (equal
+iteration counts: the per-iteration cost alone), one call of each per round so
+that they alternate in one process, `repeats` rounds after a warm-up round.  Per
+run: kernel ms (best and every value), codewords per second, mean iterations,
+ns per codeword and iteration, BER and FER per SNR point.  Then, under
+"fer_study", FER, BER and mean iterations at the last stage per SNR point of the
+fp64 decoder and of fixed-point ones at four channel clips C / scale, a 4-bit
+one, and two rows with the all-zero word in place of the real codeword:
+
+    python tools/ldpc_measure.py --fixed --out profiles/ldpc_fixed_measure.json
 """
 import argparse
 import json
@@ -44,21 +58,30 @@ SEED = 0x5EED0002
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form=1"]
 
 
-def kernel_resources(vpt):
-    """.amdhsa_* of k_ldpc<vpt>, or of k_ldpc_layered for vpt = None"""
+def kernel_resources(vpt=None, kernel="k_ldpc"):
+    """.amdhsa_* of `kernel`: k_ldpc (its instance <vpt>), k_ldpc_layered or k_ldpc_fixed"""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    unit = "kernels_ldpc.hip" if vpt is not None else "kernels_ldpc_layered.hip"
+    unit = {"k_ldpc": "kernels_ldpc.hip", "k_ldpc_layered": "kernels_ldpc_layered.hip", "k_ldpc_fixed": "kernels_ldpc_fixed.hip"}[kernel]
     with tempfile.TemporaryDirectory() as d:
         out = os.path.join(d, "k.s")
         subprocess.run([hipcc] + FLAGS + ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(PKG, "csrc"),
                                           "--cuda-device-only", "-S", os.path.join(PKG, "csrc", unit),
                                           "-o", out], check=True, capture_output=True)
         txt = open(out).read()
-    name = r"6k_ldpcILi%dE" % vpt if vpt is not None else "14k_ldpc_layeredE"
+    name = {"k_ldpc": r"6k_ldpcILi%sE" % vpt, "k_ldpc_layered": "14k_ldpc_layeredE", "k_ldpc_fixed": "12k_ldpc_fixedE"}[kernel]
     m = re.search(r"\.amdhsa_kernel (\S*%s\S*)\n(.*?)\.end_amdhsa_kernel" % name, txt, re.S)
     f = dict(re.findall(r"\.amdhsa_(\w+) (\S+)", m.group(2)))
     return {"kernel": m.group(1), "vgprs": int(f["next_free_vgpr"]), "sgprs": int(f["next_free_sgpr"]),
             "lds_static_bytes": int(f["group_segment_fixed_size"]), "scratch_bytes": int(f["private_segment_fixed_size"])}
+
+
+def fixed_thread_cap():
+    """DSCE_LDPC_FIXED_MAX_THREADS as kernels_ldpc_fixed.hip defines it, or as DSCE_LDPC_FIXED_MAX_THREADS in the
+    environment says for a library built with the macro overridden"""
+    if os.environ.get("DSCE_LDPC_FIXED_MAX_THREADS"):
+        return int(os.environ["DSCE_LDPC_FIXED_MAX_THREADS"])
+    txt = open(os.path.join(PKG, "csrc", "kernels_ldpc_fixed.hip")).read()
+    return int(re.search(r"^#define DSCE_LDPC_FIXED_MAX_THREADS\s+(\d+)", txt, re.M).group(1))
 
 
 def layer_shape(code, layers):
@@ -79,10 +102,13 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--alpha", type=float, default=0.75)
     ap.add_argument("--schedule", choices=("flooding", "layered", "compare"), default="flooding")
+    ap.add_argument("--fixed", action="store_true", help="k_ldpc_fixed against k_ldpc, alternating (see above)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
+    if a.fixed:
+        a.schedule = "fixed"
 
-    from dsce.coding import make_code, make_layers, make_ldpc
+    from dsce.coding import ldpc_encode, ldpc_fixed_lds_bytes, make_code, make_fixed, make_layers, make_ldpc
     from dsce.configs import build_setup
     from dsce.engine import build_engine, gpu_tx
     S = build_setup("default", schemes=("ofdm",), tx=gpu_tx(0))
@@ -118,6 +144,58 @@ def main(argv=None):
                 "ber": (out["bit_err"] / (a.reps * float(code.n_info))).tolist(),
                 "fer": (out["frame_err"] / float(a.reps)).tolist()}
 
+    for rate in ("1/2", "3/4") if a.schedule == "fixed" else ():
+        code = make_ldpc(B, rate, max_iter=a.iters, alpha=a.alpha)
+        full = code._replace(early_stop=False)
+        word = ldpc_encode(np.random.RandomState(11).randint(0, 2, code.n_info), code)
+        offset = make_fixed()
+        norm = make_fixed(6, 6, 8, scale=2.0, alpha_num=3, alpha_shift=2, beta=0)
+        runs = [("fp64", code, None, "k_ldpc"), ("fixed_offset1", code, offset, "k_ldpc_fixed"),
+                ("fixed_alpha3_4", code, norm, "k_ldpc_fixed"), ("fp64_all_iterations", full, None, "k_ldpc"),
+                ("fixed_all_iterations", full, offset, "k_ldpc_fixed")]
+        kd, outs = {k: [] for k, _, _, _ in runs}, {}
+        for rnd in range(a.repeats + 1):                     # round 0 warms up (buffers, clocks, code objects)
+            for key, c, fx, name in runs:
+                ms, w, outs[key] = timed(lambda: eng.run_ldpc(0, SEED, 0, a.reps, c, fixed=fx,
+                                                              codeword=word if fx is not None else None), (name,))
+                if rnd:
+                    kd[key].append(ms[name])
+        r = {key: entry(c, outs[key], kd[key]) for key, c, fx, name in runs}
+        for key, c, fx, name in runs:
+            r[key]["fixed"] = dict(fx._asdict()) if fx is not None else None
+        r["fixed_over_fp64"] = {"early_stop": r["fixed_offset1"]["kernel_ms_best"] / r["fp64"]["kernel_ms_best"],
+                                "all_iterations": r["fixed_all_iterations"]["kernel_ms_best"] /
+                                r["fp64_all_iterations"]["kernel_ms_best"]}
+        r.update({"info_bits": code.n_info, "n_checks": code.n_checks, "edges": int(code.col.size),
+                  "lds_dynamic_bytes_per_block": {"k_ldpc": 8 * code.n_vars + 24 * code.n_checks + 8,
+                                                  "k_ldpc_fixed": ldpc_fixed_lds_bytes(code.n_vars, code.n_checks)},
+                  "threads_per_block_fixed": min(fixed_thread_cap(), (max(code.n_vars, code.n_checks) + 63) // 64 * 64)})
+        # what the word length costs on this channel: FER / BER / iterations at the last stage, per SNR point, of the
+        # fp64 decoder and of fixed-point ones at three channel clips C / scale, one 4-bit decoder, and one row with
+        # the all-zero word in place of the real codeword (optimistic at ties: include/dsce.h)
+        study = [("fp64 alpha %g" % a.alpha, None, None),
+                 ("6/6/8 offset 1, clip 124", make_fixed(6, 6, 8, scale=0.25), word),
+                 ("6/6/8 offset 1, clip 31", make_fixed(6, 6, 8, scale=1.0), word),
+                 ("6/6/8 offset 1, clip 15.5", offset, word),
+                 ("6/6/8 offset 1, clip 7.75", make_fixed(6, 6, 8, scale=4.0), word),
+                 ("6/6/8 alpha 3/4, clip 15.5", norm, word),
+                 ("4/4/6 offset 1, clip 7", make_fixed(4, 4, 6, scale=1.0), word),
+                 ("4/4/6 offset 1, clip 7, all-zero word", make_fixed(4, 4, 6, scale=1.0), None),
+                 ("6/6/8 offset 1, clip 15.5, all-zero word", offset, None)]
+        r["fer_study"] = {}
+        for label, fx, w in study:
+            o = outs["fp64"] if fx is None else outs["fixed_offset1"] if (fx is offset and w is word) else \
+                outs["fixed_alpha3_4"] if fx is norm else eng.run_ldpc(0, SEED, 0, a.reps, code, fixed=fx, codeword=w)
+            r["fer_study"][label] = {"fixed": dict(fx._asdict()) if fx is not None else None,
+                                     "real_codeword": w is not None if fx is not None else None,
+                                     "fer_last_stage": (o["frame_err"][:, -1] / float(a.reps)).tolist(),
+                                     "ber_last_stage": (o["bit_err"][:, -1] / (a.reps * float(code.n_info))).tolist(),
+                                     "mean_iter_last_stage": (o["iter_sum"][:, -1] / float(a.reps)).tolist()}
+        try:
+            r["k_ldpc_fixed_resources"] = kernel_resources(kernel="k_ldpc_fixed")
+        except Exception as e:
+            r["k_ldpc_fixed_resources"] = {"error": str(e)[:200]}
+        res["rates"][rate] = r
     for rate in ("1/2", "3/4") if a.schedule == "compare" else ():
         code = make_ldpc(B, rate, max_iter=a.iters, alpha=a.alpha)
         layers = make_layers(code)
@@ -135,11 +213,11 @@ def main(argv=None):
                   "lds_dynamic_bytes_per_block": 8 * code.n_vars + 24 * code.n_checks + 8})
         r.update(layer_shape(code, layers))
         try:
-            r["k_ldpc_layered_resources"] = kernel_resources(None)
+            r["k_ldpc_layered_resources"] = kernel_resources(kernel="k_ldpc_layered")
         except Exception as e:
             r["k_ldpc_layered_resources"] = {"error": str(e)[:200]}
         res["rates"][rate] = r
-    for rate in ("1/2", "3/4") if a.schedule != "compare" else ():
+    for rate in ("1/2", "3/4") if a.schedule in ("flooding", "layered") else ():
         r = {}
         for early in (1, 0):
             code = make_ldpc(B, rate, max_iter=a.iters, alpha=a.alpha, early_stop=bool(early))
@@ -170,7 +248,7 @@ def main(argv=None):
                   "four_cycles": code.four_cycles, "threads_per_block": nt, "variables_per_thread": vpt,
                   "lds_dynamic_bytes_per_block": 8 * code.n_vars + 24 * code.n_checks + 8})
         try:
-            r["k_ldpc_resources"] = kernel_resources(None if layered else vpt)
+            r["k_ldpc_resources"] = kernel_resources(vpt, kname)
             if layered:
                 r.update(layer_shape(code, layers))
         except Exception as e:                               # no compiler here: the run is still measured
